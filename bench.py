@@ -16,7 +16,13 @@ line.  Weak scaling: per-GPU batch fixed.
 1 SegUNet_F({'label-hr': []}): resnet34-UNet + multiclass Dice in the backward path).  `--backend gloo` runs the N > 1
 path without RCCL (tests; both ranks may share one GPU with RDST_BENCH_ONE_GPU=1).
 
-Extra objects on the line (N = 1, rank 0):
+A plain run only sets up, warms up, times the `--steps` steps and prints the line (`ms_per_step` = one timed step).
+`--dump-outputs DIR` then writes what the last timed step left its caller, as float32 .npy files (at most 64 MB in all;
+a fixed, seeded sample of each array if they would be larger): loss.npy (the returned loss), params.npy (the flat fp32
+parameters after Adam) and grads.npy (the flat fp32 gradient bucket).  The inputs are seeded, so two builds run with the
+same arguments can be compared file by file.
+
+Extra objects on the line, with `--full` only (N = 1, rank 0):
   roofline     — the window-attention forward kernel (K1): algorithmic bytes (4*C*elt per token per launch,
                  DESIGN.md) / its average duration, vs 8 TB/s HBM.  `frac` is the COLD figure: the step's 48 K1
                  launches (recorded through the C ABI while the step graph was captured) replayed back to back on
@@ -31,7 +37,7 @@ Extra objects on the line (N = 1, rank 0):
   parity_mode  — the same step in the fp32x3 mode (fp32 tensors, split-bf16 GEMMs): the fast mode that holds the 4-decimal bar.
   cpu_baseline — the CPU oracle (oracle/rdst_oracle.py, a port) timed on the host cores on a bounded
                  sample (batch 4) of the same workload.
-  configs      — (default run only: --config e1, N = 1) the OTHER BASELINE.json configurations on the same line, 5 timed
+  configs      — (--full with --config e1, N = 1) the OTHER BASELINE.json configurations on the same line, 5 timed
                  graph steps each after capture: ws16 (configs[3]: value, ms_per_step, K1 / K2 roofline fractions),
                  e1_unetf and e1_hrl (configs[4]: value, ms_per_step, the loss network's share of the step), each with its
                  own cpu_baseline (oracle + oracle/segunet_oracle.py at batch 1).  `--no-configs` skips them.
@@ -333,6 +339,24 @@ def cpu_baseline_collect(h):
                       f"the three configs[3] / configs[4] samples timed side by side (16 threads each of {host['host_logical_cpus']} CPUs)"}
 
 
+DUMP_BUDGET_BYTES = 63 * 10 ** 6   # array data; the .npy headers stay far inside the 64 MB cap
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write every tensor of `arrays` as dirname/<name>.npy in float32.  If they would exceed `budget` bytes together, every
+    array keeps the same fraction of its elements, at sorted indices drawn from a fixed seed (identical from run to run for
+    arrays of the same size)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    host = {n: t.detach().float().reshape(-1).cpu().numpy() for n, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    for i, (n, a) in enumerate(host.items()):
+        if total > budget:
+            keep = max(1, a.size * budget // total)
+            a = a[np.sort(np.random.default_rng(i).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(dirname, n + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     if len(sys.argv) >= 5 and sys.argv[1] == "--cpu-baseline-worker":
         _cpu_baseline_worker(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), sys.argv[5] if len(sys.argv) > 5 else "e1")
@@ -353,12 +377,19 @@ def main():
                     help="initialise the process group and run its collectives (broadcast, bucket all-reduce) even with ONE rank: "
                          "executes the RCCL path on a one-GPU box (launch through torch.distributed.run --nproc-per-node 1)")
     ap.add_argument("--graph", type=int, default=1, help="replay the step from a HIP graph")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write loss / params / grads of the last step as DIR/<name>.npy (float32, <= 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-kernel / roofline tables, the fp32 and fp32x3 modes, the "
+                         "other BASELINE configurations and the CPU baselines (the --no-* options below switch parts off)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--roofline-steps", type=int, default=3, help="replay passes over the recorded launches")
     ap.add_argument("--no-roofline", action="store_true", help="skip the per-op measurements (clean per-step kernel profiles)")
     ap.add_argument("--no-fp32-line", action="store_true", help="skip the fp32 parity-mode measurement (field fp32_mode)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the other BASELINE configurations (field configs) of the default run")
+    ap.add_argument("--no-configs", action="store_true", help="skip the other BASELINE configurations (field configs) of the --full run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -410,15 +441,17 @@ def main():
 
     lib = _lib.load()
     rec = Recorder(lib)
-    # the other BASELINE configurations ride on the default run's line
-    want_configs = (rank == 0 and world == 1 and args.config == "e1" and args.dtype == "bf16" and not args.no_configs
-                    and not args.no_roofline)
+    # everything beside the headline (per-op tables, other modes and configurations, CPU baselines) is --full only
+    extras = args.full and rank == 0 and world == 1 and not args.no_roofline
+    # the other BASELINE configurations ride on the --full run's line
+    want_configs = extras and args.config == "e1" and args.dtype == "bf16" and not args.no_configs
     if args.graph:
         for _ in range(2):          # eager steps: every lazy initialisation (weight-image plans, workspaces) happens here
             tr.step(x, tgt)
         torch.cuda.synchronize()
         tr.use_graph = True
-        tr.capture_hook = lambda: rec   # the step graph's pool keeps every recorded operand alive
+        if extras:
+            tr.capture_hook = lambda: rec   # the step graph's pool keeps every recorded operand alive
         if not tr.capture(x, tgt) and rank == 0:
             print("bench.py: graph capture failed; running eagerly", file=sys.stderr)
         tr.capture_hook = None
@@ -435,9 +468,11 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        tr.step(x, tgt)
+        last_loss = tr.step(x, tgt)
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:   # before anything below touches the bucket (the N > 1 all-reduce timing rewrites it)
+        dump_outputs(args.dump_outputs, {"loss": last_loss, "params": tr.optimizer.flat_param, "grads": bucket.flat})
     loss_t = tr._loss_buf.detach().clone().double()
     param_sync = None
     if use_pg:
@@ -503,11 +538,11 @@ def main():
             dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         out["unet_bn_batches_tracked"] = [int(lo.item()), int(hi.item())]
 
-    if rank == 0 and world == 1 and not args.no_roofline and tr.graph is not None and recorded:
+    if extras and tr.graph is not None and recorded:
         elt = 2 if args.dtype == "bf16" else 4
         reps = max(1, args.roofline_steps)
         out.update(op_tables(lib, recorded, elt, reps, args.dtype, net, x, ws16=(args.config == "ws16")))
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if extras:
         if args.dtype == "bf16" and not args.no_fp32_line and args.config == "e1":
             # the parity mode (fp32 activations, exact-fp32 MFMA): the only mode with the 4-decimal PSNR claim
             del tr

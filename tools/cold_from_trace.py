@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""From a rocprofv3 --kernel-trace CSV of `python3 bench.py` (roofline on): separate the COLD REPLAY launches of an op — the
+"""From a rocprofv3 --kernel-trace CSV of `python3 bench.py --full` (roofline on): separate the COLD REPLAY launches of an op — the
 runs of >= `minrun` consecutive dispatches of kernels whose name contains `sub`, with nothing else in between: that is how
 bench.py replays the recorded launches of one C-ABI entry point back to back — from its launches inside training steps, and
 print the average duration of both populations (per kernel variant).
