@@ -348,35 +348,55 @@ def test_conv_fp32_channel_slices(B, H, W, Cin, Cout, res, scale, r):
 # ------------------------------------------------------------------------------------------------------------------
 # The network: RDST-E1 x4 (BASELINE.json configs[1] architecture), bf16, forward + L1 + backward vs the oracle
 # ------------------------------------------------------------------------------------------------------------------
-def _e1_all_gradients(B):
+def _e1_oracle(B):
+    """The oracle's forward + L1 + backward of RDST-E1 x4 (weights of seed 11, inputs from generator 1234) at batch B."""
     from util import build_net
     cfg = O.CFG_E1
     sd = O.make_weights(cfg, 11)
-    net = build_net(cfg)
-    net.load_state_dict(sd, strict=True)
-    net.to(DEV).train().set_compute_dtype(torch.bfloat16)
+    trainable = {k for k, p in build_net(cfg).named_parameters() if p.requires_grad}
     g = torch.Generator().manual_seed(1234)
     x = torch.rand(B, 1, 64, 64, generator=g)
     tgt = torch.rand(B, 1, 256, 256, generator=g)
-    y = net(x.to(DEV))
-    loss = F.l1_loss(y, tgt.to(DEV))
-    loss.backward()
-    torch.cuda.synchronize()
-
-    params = dict(net.named_parameters())
-    osd = {k: (v.clone().requires_grad_(True) if (k in params and params[k].requires_grad) else v) for k, v in sd.items()}
+    osd = {k: (v.clone().requires_grad_(True) if k in trainable else v) for k, v in sd.items()}
     oy = O.rdstsr_forward(x, osd, cfg)
     oloss = F.l1_loss(oy, tgt)
     oloss.backward()
+    return {"cfg": cfg, "sd": sd, "x": x, "tgt": tgt, "oy": oy.detach(), "oloss": oloss.item(),
+            "grads": {k: osd[k].grad for k in trainable}}
 
-    yc = y.detach().float().cpu()
-    dpsnr = abs(O.psnr(tgt, yc, 4) - O.psnr(tgt, oy.detach(), 4))
+
+@pytest.fixture(scope="module")
+def e1_oracle_b32():
+    """The batch-32 oracle pass, computed once for the bf16 and the fp32x3 tests at the bench batch."""
+    return _e1_oracle(32)
+
+
+def _e1_net_step(orc, dtype):
+    """The HIP network's forward + L1 + backward on the oracle pass's weights and inputs in compute mode `dtype`."""
+    from util import build_net
+    net = build_net(orc["cfg"])
+    net.load_state_dict(orc["sd"], strict=True)
+    net.to(DEV).train().set_compute_dtype(dtype)
+    y = net(orc["x"].to(DEV))
+    loss = F.l1_loss(y, orc["tgt"].to(DEV))
+    loss.backward()
+    torch.cuda.synchronize()
+    return net, y.detach().float().cpu(), loss.item()
+
+
+def _e1_all_gradients(B, orc=None):
+    orc = orc if orc is not None else _e1_oracle(B)
+    net, yc, loss = _e1_net_step(orc, torch.bfloat16)
+    params = dict(net.named_parameters())
+    tgt, oy, oloss = orc["tgt"], orc["oy"], orc["oloss"]
+
+    dpsnr = abs(O.psnr(tgt, yc, 4) - O.psnr(tgt, oy, 4))
     worst, tot_d, tot_r, n = (0.0, None), 0.0, 0.0, 0
     bad = []
     for k, p in params.items():
         if not p.requires_grad:
             continue
-        ref = osd[k].grad
+        ref = orc["grads"][k]
         assert p.grad is not None and ref is not None, k
         d = (p.grad.float().cpu() - ref).norm().item()
         rn = ref.norm().item()
@@ -389,11 +409,11 @@ def _e1_all_gradients(B):
         if rel > 3e-2:
             bad.append((k, rel))
     total = (tot_d / tot_r) ** 0.5
-    print(f"\nE1 bf16 B={B}: |dPSNR| {dpsnr:.2e} dB  out max|d| {(yc - oy.detach()).abs().max().item():.2e}  "
-          f"loss {loss.item():.6f} vs {oloss.item():.6f}  {n} gradients: total rel L2 {total:.2e}, worst {worst[0]:.2e} "
+    print(f"\nE1 bf16 B={B}: |dPSNR| {dpsnr:.2e} dB  out max|d| {(yc - oy).abs().max().item():.2e}  "
+          f"loss {loss:.6f} vs {oloss:.6f}  {n} gradients: total rel L2 {total:.2e}, worst {worst[0]:.2e} "
           f"({worst[1]})")
     assert n == 750
-    assert dpsnr < 0.05 and abs(loss.item() - oloss.item()) <= 2e-3
+    assert dpsnr < 0.05 and abs(loss - oloss) <= 2e-3
     assert total <= 1.2e-2
     assert not bad, bad[:10]
 
@@ -405,9 +425,43 @@ def test_e1_bf16_train_step_all_gradients_vs_oracle():
     _e1_all_gradients(8)
 
 
-def test_e1_bf16_train_step_all_gradients_vs_oracle_bench_batch():
+def test_e1_bf16_train_step_all_gradients_vs_oracle_bench_batch(e1_oracle_b32):
     """The same at THE batch bench.py runs (BASELINE configs[1]: B = 32, 2048 windows per Swin block)."""
-    _e1_all_gradients(32)
+    _e1_all_gradients(32, e1_oracle_b32)
+
+
+def test_e1_fp32x3_train_step_all_gradients_vs_oracle_bench_batch(e1_oracle_b32):
+    """The parity mode bench.py reports (`parity_mode`: fp32x3) at THE batch it runs, B = 32 (131072 tokens, 2048 windows per
+    Swin block, 4096 row tiles per Linear), against the same oracle pass, with the gates of the batch-4 test
+    (test_fp32x3_gpu.py::test_e1_fp32x3_bench_shape_psnr_equal_to_4_decimals): |dPSNR| < 5e-5 dB at border 4, loss to 2e-6,
+    every one of the 750 gradients to 1e-3 relative L2 (the relative-position bias tables to 2.5e-3), the total gradient to
+    2e-4; and the SR images to 2e-4 max|d| over all 32 (the fp32x3-vs-exact bound)."""
+    from rdst_amd import ops
+    orc = e1_oracle_b32
+    net, yc, loss = _e1_net_step(orc, "fp32x3")
+    tgt, oy, oloss = orc["tgt"], orc["oy"], orc["oloss"]
+    params = {k: p for k, p in net.named_parameters() if p.requires_grad}
+    rels = [((p.grad.cpu() - orc["grads"][k]).norm().item() / max(orc["grads"][k].norm().item(), 1e-12), k)
+            for k, p in params.items()]
+    is_table = lambda k: k.endswith("relative_position_bias_table")
+    worst_tab = max(r for r in rels if is_table(r[1]))
+    worst_rest = max(r for r in rels if not is_table(r[1]))
+    num = sum((p.grad.cpu() - orc["grads"][k]).double().pow(2).sum().item() for k, p in params.items())
+    den = sum(orc["grads"][k].double().pow(2).sum().item() for k in params)
+    total = (num / den) ** 0.5
+    p_hip, p_ref = O.psnr(tgt, yc, 4), O.psnr(tgt, oy, 4)
+    dy = (yc - oy).abs().max().item()
+    print(f"\nE1 fp32x3 B=32: PSNR {p_hip:.6f} vs {p_ref:.6f} dB (|d| {abs(p_hip - p_ref):.2e})  out max|d| {dy:.2e}  "
+          f"loss {loss:.7f} vs {oloss:.7f}  {len(rels)} gradients: total {total:.2e}, worst table {worst_tab[0]:.2e} "
+          f"({worst_tab[1]}), worst other {worst_rest[0]:.2e} ({worst_rest[1]})")
+    assert net.compute_code == ops.F32X3
+    assert len(rels) == 750
+    assert abs(p_hip - p_ref) < 5e-5
+    assert abs(loss - oloss) <= 2e-6
+    assert worst_rest[0] <= 1e-3, worst_rest
+    assert worst_tab[0] <= 2.5e-3, worst_tab
+    assert total <= 2e-4
+    assert dy <= 2e-4
 
 
 def _ws16_all_gradients(dtype, B, tol_tensor, tol_total, tol_dpsnr, tol_loss):

@@ -132,3 +132,46 @@ def model_kwargs(kw):
     if "norm_layer" in kw:
         kw["norm_layer"] = {"identity": nn.Identity, "layernorm": nn.LayerNorm}[kw["norm_layer"]]
     return kw
+
+
+def local_rel(got, want, tiles):
+    """Tile-local relative error: ||got - want|| / ||want|| over each block of a tiling, in float64.
+
+    `tiles` maps a dimension to its block length along that dimension ({0: 32, 1: 32}: 32 x 32 tiles of a matrix;
+    {0: 1}: one row per block); a dimension not named is taken whole.  A dimension that is not a multiple of its block
+    length is zero-padded, so the ragged last block is measured on its real elements, never dropped.  Returns
+    (worst, median, index of the worst block), the index as a tuple of block coordinates in the order of sorted(tiles).
+    A single relative L2 over a whole tensor lets one bad tile hide among thousands of good ones; this does not."""
+    import torch.nn.functional as F
+    want = want.to(dtype=torch.float64)
+    err = got.to(device=want.device, dtype=torch.float64) - want
+    if err.shape != want.shape:
+        raise ValueError(f"local_rel: shapes {tuple(got.shape)} and {tuple(want.shape)} differ")
+    blk = {d % want.dim(): int(b) for d, b in tiles.items()}
+    pad = []
+    for d in reversed(range(want.dim())):
+        b = blk.get(d)
+        pad += [0, (-want.shape[d]) % b if b else 0]
+    if any(pad):
+        err, want = F.pad(err, pad), F.pad(want, pad)
+    shape, order, n = [], [], 0
+    for d, s in enumerate(want.shape):
+        if d in blk:
+            shape += [s // blk[d], blk[d]]
+            order.append(n)
+            n += 2
+        else:
+            shape.append(s)
+            n += 1
+    rest = [i for i in range(n) if i not in order]
+    perm = order + rest
+    e2 = err.reshape(shape).permute(perm).reshape(*[shape[i] for i in order], -1).pow(2).sum(-1)
+    w2 = want.reshape(shape).permute(perm).reshape(*[shape[i] for i in order], -1).pow(2).sum(-1)
+    rel = (e2.sqrt() / w2.sqrt().clamp_min(1e-300)).flatten()
+    i = int(rel.argmax())
+    grid = [shape[j] for j in order]
+    idx = []
+    for g in reversed(grid):
+        idx.append(i % g)
+        i //= g
+    return rel.max().item(), rel.median().item(), tuple(reversed(idx))
