@@ -263,14 +263,16 @@ int rdst_swin_attn_fwd(const void* X, int64_t ld_x, const float* ln_w, const flo
  * Conv forward: W (Cout = N, Cin = K, 3, 3), s = out_scale. */
 #define RDST_PREPACKED ((size_t)-1)
 #define RDST_PACK_LINEAR 0
-#define RDST_PACK_CONV3_FWD 1
+#define RDST_PACK_CONV3_FWD 1      /* rdst_conv_fwd reads it only when the image width W % 32 == 0 (the packable query does not see W:
+                                      on other widths the image is packed and unused) */
 #define RDST_PACK_LINEAR_SEC3 2   /* a Linear whose N = 3 C outputs are the sections q | k | v, each padded to whole 32-row tiles
                                      (the qkv half of rdst_swin_attn_fwd's workspace; N % 3 == 0) */
 #define RDST_PACK_LINEAR_X3 3     /* the RDST_F32X3 image of a Linear: hi / lo bf16 fragment pairs + b' (what rdst_ln_linear_fwd reads with
                                      dtype = RDST_F32X3 on the shapes rdst_ln_linear_fwd_packable reports; `out` needs
                                      rdst_ln_linear_fwd_workspace2(K, N, RDST_F32X3) bytes) */
 #define RDST_PACK_CONV3_FWD_X3 4  /* the RDST_F32X3 image of a 3x3 convolution's forward weights (rdst_conv_fwd with dtype = RDST_F32X3 on the
-                                     shapes rdst_conv_fwd_packable reports; `out` needs rdst_conv_fwd_workspace2(Cin, Cout, 3, RDST_F32X3)) */
+                                     shapes rdst_conv_fwd_packable reports; `out` needs rdst_conv_fwd_workspace2(Cin, Cout, 3, RDST_F32X3));
+                                     read only when W % 32 == 0, like RDST_PACK_CONV3_FWD */
 typedef struct rdst_pack_job {
   int kind;
   const float* W; const float* gamma; const float* beta; const float* bias;

@@ -66,19 +66,20 @@ static inline int rdst_launch_status(const char* what) {
   return 0;
 }
 
-// RDST_F32X3 on the network entry points: fp32 tensors, GEMMs in the split arithmetic of mfma.h (Mma<float, true>).
-// The entry point opens a SplitScope, which turns the dtype into RDST_F32 for everything below it and leaves the mode in
-// a thread-local that the launchers of the converted kernels read (kernels without a split form run exact fp32).
-extern thread_local int g_rdst_split;
-struct SplitScope {
-  int prev;
-  explicit SplitScope(int& dtype) : prev(g_rdst_split) {
-    g_rdst_split = dtype == RDST_F32X3 || (prev && dtype == RDST_F32);   // (an entry point that forwards to another one keeps the mode)
-    if (dtype == RDST_F32X3) dtype = RDST_F32;
-  }
-  ~SplitScope() { g_rdst_split = prev; }
-};
-static inline bool rdst_split() { return g_rdst_split != 0; }
+// The compute mode of an entry point's dtype, decoded first thing: `dtype` becomes the element type of the rows (RDST_BF16 or
+// RDST_F32) and `split` says whether the GEMMs run in the split arithmetic of mfma.h (RDST_F32X3: fp32 rows, Mma<float, true>).
+// The launchers take `split` as an argument and pick their <..., true> instantiation from it; kernels without a split form run
+// exact fp32.  Unknown values are refused.
+static inline int rdst_dtype(int& dtype, bool& split, const char* who) {
+  if (dtype != RDST_BF16 && dtype != RDST_F32 && dtype != RDST_F32X3) return rdst_fail(RDST_EINVAL, "%s: bad dtype %d", who, dtype);
+  split = dtype == RDST_F32X3;
+  if (split) dtype = RDST_F32;
+  return 0;
+}
+static inline int rdst_dtype(int& dtype, const char* who) {   // (an entry point without split kernels)
+  bool split;
+  return rdst_dtype(dtype, split, who);
+}
 
 template <typename T> __device__ __forceinline__ float to_f32(T v);
 template <> __device__ __forceinline__ float to_f32<float>(float v) { return v; }

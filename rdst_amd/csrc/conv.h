@@ -33,17 +33,18 @@ struct ConvGeom {
 
 template <typename T>
 int conv_fwd_mfma(const T* X, int64_t ldx, int in_act, const float* Wc, const float* bias, const T* R, int64_t ldr,
-                  T* Y, int64_t ldy, const ConvGeom& g, float s, hipStream_t st);
+                  T* Y, int64_t ldy, const ConvGeom& g, float s, bool split, hipStream_t st);
+// split (fp32 rows only): the RDST_F32X3 form of the kernels (common.h).
 // The two backward hooks take dY as PLAIN rows (B*H*W, Cout): plain_dy() un-shuffles a pixel-shuffled
 // dY into scratch once (or returns dY itself when r == 1).
 template <typename T>
 const T* plain_dy(const T* dY, int64_t lddy, const ConvGeom& g, void* scratch, int64_t& ld_out, hipStream_t st, int& rc);
 template <typename T>
 int conv_dgrad_mfma(const T* X, int64_t ldx, int in_act, const float* Wc, const T* dYp, int64_t lddyp, T* dX,
-                    int64_t lddx, const T* acc, int64_t ldacc, const ConvGeom& g, float s, hipStream_t st);
+                    int64_t lddx, const T* acc, int64_t ldacc, const ConvGeom& g, float s, bool split, hipStream_t st);
 template <typename T>
 int conv_wgrad_mfma(const T* X, int64_t ldx, int in_act, const T* dYp, int64_t lddyp, float* dW, float* dbias,
-                    float* slab, const ConvGeom& g, float s, hipStream_t st);
+                    float* slab, const ConvGeom& g, float s, bool split, hipStream_t st);
 size_t conv_mfma_scratch_bytes(const ConvGeom& g);
 
 // one-output-channel 3x3 conv (the tail conv) and the 1 -> 1 channel 1x1 conv (MeanShift), bf16: plain vector kernels
@@ -65,6 +66,7 @@ size_t conv_in1_slab_floats(int Cout);
 // register-stationary 3x3 kernels for the E1 shapes, bf16 (conv3_mfma.hip); RDST_ENOTSUP for everything else.
 // wpack: conv3_pack_bytes(Cin, Cout) bytes of 16-byte aligned device scratch (NULL -> RDST_ENOTSUP).
 size_t conv3_pack_bytes(int Cin, int Cout);
+int conv3_fwd_shape(int Cin, int Cout, int ks, int r, bool has_res, int in_act);   // 0 = not covered
 int conv3_fwd_bf16(const bf16* X, int64_t ldx, int in_act, const float* Wc, const float* bias, const bf16* R, int64_t ldr,
                    bf16* Y, int64_t ldy, const ConvGeom& g, float s, void* wpack, bool prepacked, hipStream_t st);
 int conv3_dgrad_bf16(const float* Wc, const bf16* dY, int64_t lddy, bf16* dX, int64_t lddx, const bf16* acc, int64_t ldacc,

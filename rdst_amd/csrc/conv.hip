@@ -129,7 +129,7 @@ int wgrad_splits(const ConvGeom& g) {
 
 template <typename T>
 int fwd_t(const T* X, int64_t ldx, int in_act, const float* Wc, const float* bias, const T* R, int64_t ldr, T* Y,
-          int64_t ldy, const ConvGeom& g, float s, void* wpack, bool prepacked, hipStream_t st) {
+          int64_t ldy, const ConvGeom& g, float s, void* wpack, bool prepacked, bool split, hipStream_t st) {
   if constexpr (sizeof(T) == 2) {
     if (int rc = conv_c1_fwd_bf16(X, ldx, in_act, Wc, bias, R, ldr, Y, ldy, g, s, st); rc != RDST_ENOTSUP) return rc;
     if (int rc = conv_in1_fwd_bf16(X, ldx, in_act, Wc, bias, R, ldr, Y, ldy, g, s, st); rc != RDST_ENOTSUP) return rc;
@@ -140,10 +140,10 @@ int fwd_t(const T* X, int64_t ldx, int in_act, const float* Wc, const float* bia
     if (int rc = conv_in1x_fwd_f32(X, ldx, in_act, Wc, bias, R, ldr, Y, ldy, g, s, st); rc != RDST_ENOTSUP) return rc;
   }
   if constexpr (sizeof(T) == 4) {   // RDST_F32X3: the register-stationary kernels on prepacked hi / lo fragments (conv3x_mfma.hip)
-    if (rdst_split())
+    if (split)
       if (int rc = conv3x_fwd_f32(X, ldx, in_act, Wc, bias, R, ldr, Y, ldy, g, s, wpack, prepacked, st); rc != RDST_ENOTSUP) return rc;
   }
-  if (int rc = conv_fwd_mfma<T>(X, ldx, in_act, Wc, bias, R, ldr, Y, ldy, g, s, st); rc != RDST_ENOTSUP) return rc;
+  if (int rc = conv_fwd_mfma<T>(X, ldx, in_act, Wc, bias, R, ldr, Y, ldy, g, s, split, st); rc != RDST_ENOTSUP) return rc;
   ConvA<T> la{X, ldx, g, in_act};
   ConvB lb{Wc, g};
   ConvFwdEp<T> ep{bias, R, ldr, Y, ldy, g, s};
@@ -152,7 +152,7 @@ int fwd_t(const T* X, int64_t ldx, int in_act, const float* Wc, const float* bia
 
 template <typename T>
 int bwd_t(const T* X, int64_t ldx, int in_act, const float* Wc, const T* dY, int64_t lddy, T* dX, int64_t lddx,
-          const T* acc, int64_t ldacc, float* dW, float* dbias, float* wsp, const ConvGeom& g, float s, hipStream_t st) {
+          const T* acc, int64_t ldacc, float* dW, float* dbias, float* wsp, const ConvGeom& g, float s, bool split, hipStream_t st) {
   const int64_t wtotal = (int64_t)g.Cout * g.Cin * g.ks * g.ks;
   // workspace carve: [packed dgrad weights][generic split-K slab][small][MFMA scratch: un-shuffled dY, wgrad slab]
   void* wpack = wsp;
@@ -193,12 +193,12 @@ int bwd_t(const T* X, int64_t ldx, int in_act, const float* Wc, const T* dY, int
     if ((dxdone || !dX) && !dW && !dbias) return 0;
   }
   if constexpr (sizeof(T) == 4) {   // RDST_F32X3: the register-stationary dgrad (conv3x_mfma.hip)
-    if (dX && rdst_split()) {
+    if (dX && split) {
       const int rc = conv3x_dgrad_f32(Wc, dY, lddy, dX, lddx, acc, ldacc, in_act, g, s, wpack, st);
       if (rc == 0) dxdone = true;
       else if (rc != RDST_ENOTSUP) return rc;
     }
-    if ((dW || dbias) && rdst_split()) {   // ... and weight gradient (conv3x_wgrad.hip): the shuffled dY as it lies
+    if ((dW || dbias) && split) {   // ... and weight gradient (conv3x_wgrad.hip): the shuffled dY as it lies
       const int rc = conv3x_wgrad_f32(X, ldx, in_act, dY, lddy, dW, dbias, w3slab, g, s, st);
       if (rc == 0) { dW = nullptr; dbias = nullptr; }
       else if (rc != RDST_ENOTSUP) return rc;
@@ -213,7 +213,7 @@ int bwd_t(const T* X, int64_t ldx, int in_act, const float* Wc, const T* dY, int
   float* mslab = reinterpret_cast<float*>(mscr + (g.r > 1 ? (size_t)g.pixels() * g.Cout * 4 : 0));
   bool wdone = false;
   if (dW || dbias) {
-    const int rc = conv_wgrad_mfma<T>(X, ldx, in_act, dYp, ldp, dW, dbias, mslab, g, s, st);
+    const int rc = conv_wgrad_mfma<T>(X, ldx, in_act, dYp, ldp, dW, dbias, mslab, g, s, split, st);
     if (rc == 0) wdone = true;
     else if (rc != RDST_ENOTSUP) return rc;
   }
@@ -232,7 +232,7 @@ int bwd_t(const T* X, int64_t ldx, int in_act, const float* Wc, const T* dY, int
     if (rc) return rc;
   }
   if (dX && !dxdone) {
-    int rc = conv_dgrad_mfma<T>(X, ldx, in_act, Wc, dYp, ldp, dX, lddx, acc, ldacc, g, s, st);
+    int rc = conv_dgrad_mfma<T>(X, ldx, in_act, Wc, dYp, ldp, dX, lddx, acc, ldacc, g, s, split, st);
     if (rc == RDST_ENOTSUP) {
       ConvDyA<T> la{dY, lddy, g, s};
       ConvBd lb{Wc, g};
@@ -275,11 +275,10 @@ __global__ void __launch_bounds__(256) rows_to_nchw_kernel(const T* __restrict__
 }  // namespace
 
 extern "C" int rdst_conv_fwd_packable(int Cin, int Cout, int ksize, int shuffle_r, int has_residual, int in_act, int dtype) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
-  if (dtype == RDST_F32 && rdst_split()) return conv3x_fwd_shape(Cin, Cout, ksize, shuffle_r, has_residual != 0, in_act) != 0;
-  if (dtype != RDST_BF16 || ksize != 3 || in_act) return 0;
-  return (Cin == 150 && Cout == 60 && shuffle_r == 1) || (Cin == 60 && Cout == 60 && shuffle_r == 1) ||
-         (Cin == 60 && Cout == 240 && shuffle_r == 2 && !has_residual);
+  bool split;
+  if (rdst_dtype(dtype, split, "rdst_conv_fwd_packable")) return 0;
+  if (split) return conv3x_fwd_shape(Cin, Cout, ksize, shuffle_r, has_residual != 0, in_act) != 0;
+  return dtype == RDST_BF16 && conv3_fwd_shape(Cin, Cout, ksize, shuffle_r, has_residual != 0, in_act) != 0;
 }
 
 extern "C" size_t rdst_conv_fwd_workspace(int Cin, int Cout, int ksize) {
@@ -296,22 +295,22 @@ extern "C" size_t rdst_conv_fwd_workspace2(int Cin, int Cout, int ksize, int dty
 extern "C" int rdst_conv_fwd(const void* X, int64_t ld_x, int in_act, const float* Wc, const float* bias, const void* R,
                              int64_t ld_r, void* Y, int64_t ld_y, void* workspace, size_t workspace_bytes, int B, int H, int W,
                              int Cin, int Cout, int ksize, float out_scale, int shuffle_r, int dtype, void* stream) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
+  bool split;
+  if (int rc = rdst_dtype(dtype, split, "rdst_conv_fwd")) return rc;
   ConvGeom g;
   if (int rc = make_geom(g, B, H, W, Cin, Cout, ksize, shuffle_r, "rdst_conv_fwd")) return rc;
   if (!X || !Wc || !Y) return rdst_fail(RDST_EINVAL, "rdst_conv_fwd: null pointer");
   const int cy = Cout / (shuffle_r * shuffle_r);
   if (ld_x < Cin || ld_y < cy || (R && ld_r < cy)) return rdst_fail(RDST_EINVAL, "rdst_conv_fwd: leading dimension too small");
-  if (dtype != RDST_F32 && dtype != RDST_BF16) return rdst_fail(RDST_EINVAL, "rdst_conv_fwd: bad dtype %d", dtype);
   hipStream_t st = (hipStream_t)stream;
   void* wpack = (workspace && workspace_bytes >= rdst_conv_fwd_workspace(Cin, Cout, ksize)) ? workspace : nullptr;
   if (dtype == RDST_F32) {
-    void* wpx = (rdst_split() && workspace && workspace_bytes >= conv3x_pack_bytes(Cin, Cout)) ? workspace : nullptr;
+    void* wpx = (split && workspace && workspace_bytes >= conv3x_pack_bytes(Cin, Cout)) ? workspace : nullptr;
     return fwd_t<float>((const float*)X, ld_x, in_act, Wc, bias, (const float*)R, ld_r, (float*)Y, ld_y, g, out_scale, wpx,
-                        workspace_bytes == RDST_PREPACKED, st);
+                        workspace_bytes == RDST_PREPACKED, split, st);
   }
   return fwd_t<bf16>((const bf16*)X, ld_x, in_act, Wc, bias, (const bf16*)R, ld_r, (bf16*)Y, ld_y, g, out_scale, wpack,
-                     workspace_bytes == RDST_PREPACKED, st);
+                     workspace_bytes == RDST_PREPACKED, false, st);
 }
 
 extern "C" size_t rdst_conv_bwd_workspace(int B, int H, int W, int Cin, int Cout, int ksize) {
@@ -326,40 +325,38 @@ extern "C" int rdst_conv_bwd(const void* X, int64_t ld_x, int in_act, const floa
                              void* workspace,
                              size_t workspace_bytes, int B, int H, int W, int Cin, int Cout, int ksize, float out_scale,
                              int shuffle_r, int dtype, void* stream) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
+  bool split;
+  if (int rc = rdst_dtype(dtype, split, "rdst_conv_bwd")) return rc;
   ConvGeom g;
   if (int rc = make_geom(g, B, H, W, Cin, Cout, ksize, shuffle_r, "rdst_conv_bwd")) return rc;
   if (!X || !Wc || !dY || !workspace) return rdst_fail(RDST_EINVAL, "rdst_conv_bwd: null pointer");
   const int cy = Cout / (shuffle_r * shuffle_r);
   if (ld_x < Cin || ld_dy < cy || (dX && ld_dx < Cin)) return rdst_fail(RDST_EINVAL, "rdst_conv_bwd: leading dimension too small");
-  if (dtype != RDST_F32 && dtype != RDST_BF16) return rdst_fail(RDST_EINVAL, "rdst_conv_bwd: bad dtype %d", dtype);
   if (workspace_bytes < rdst_conv_bwd_workspace(B, H, W, Cin, Cout, ksize)) return rdst_fail(RDST_EINVAL, "rdst_conv_bwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   if (dtype == RDST_F32)
-    return bwd_t<float>((const float*)X, ld_x, in_act, Wc, (const float*)dY, ld_dy, (float*)dX, ld_dx, (const float*)dX_add, ld_dx_add, dW, dbias, (float*)workspace, g, out_scale, st);
-  return bwd_t<bf16>((const bf16*)X, ld_x, in_act, Wc, (const bf16*)dY, ld_dy, (bf16*)dX, ld_dx, (const bf16*)dX_add, ld_dx_add, dW, dbias, (float*)workspace, g, out_scale, st);
+    return bwd_t<float>((const float*)X, ld_x, in_act, Wc, (const float*)dY, ld_dy, (float*)dX, ld_dx, (const float*)dX_add, ld_dx_add, dW, dbias, (float*)workspace, g, out_scale, split, st);
+  return bwd_t<bf16>((const bf16*)X, ld_x, in_act, Wc, (const bf16*)dY, ld_dy, (bf16*)dX, ld_dx, (const bf16*)dX_add, ld_dx_add, dW, dbias, (float*)workspace, g, out_scale, false, st);
 }
 
 extern "C" int rdst_nchw_to_rows(const float* nchw, void* rows, int64_t ld, int B, int C, int H, int W, int dtype, void* stream) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
+  if (int rc = rdst_dtype(dtype, "rdst_nchw_to_rows")) return rc;
   if (!nchw || !rows || B <= 0 || C <= 0 || H <= 0 || W <= 0 || ld < C) return rdst_fail(RDST_EINVAL, "rdst_nchw_to_rows: bad arguments");
   const int64_t n = (int64_t)B * C * H * W;
   const dim3 grid((unsigned)((n + 255) / 256));
   hipStream_t st = (hipStream_t)stream;
   if (dtype == RDST_F32) hipLaunchKernelGGL((nchw_to_rows_kernel<float>), grid, dim3(256), 0, st, nchw, (float*)rows, ld, B, C, (int64_t)H * W);
-  else if (dtype == RDST_BF16) hipLaunchKernelGGL((nchw_to_rows_kernel<bf16>), grid, dim3(256), 0, st, nchw, (bf16*)rows, ld, B, C, (int64_t)H * W);
-  else return rdst_fail(RDST_EINVAL, "rdst_nchw_to_rows: bad dtype %d", dtype);
+  else hipLaunchKernelGGL((nchw_to_rows_kernel<bf16>), grid, dim3(256), 0, st, nchw, (bf16*)rows, ld, B, C, (int64_t)H * W);
   return rdst_launch_status("nchw_to_rows");
 }
 
 extern "C" int rdst_rows_to_nchw(const void* rows, int64_t ld, float* nchw, int B, int C, int H, int W, int dtype, void* stream) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
+  if (int rc = rdst_dtype(dtype, "rdst_rows_to_nchw")) return rc;
   if (!nchw || !rows || B <= 0 || C <= 0 || H <= 0 || W <= 0 || ld < C) return rdst_fail(RDST_EINVAL, "rdst_rows_to_nchw: bad arguments");
   const int64_t n = (int64_t)B * C * H * W;
   const dim3 grid((unsigned)((n + 255) / 256));
   hipStream_t st = (hipStream_t)stream;
   if (dtype == RDST_F32) hipLaunchKernelGGL((rows_to_nchw_kernel<float>), grid, dim3(256), 0, st, (const float*)rows, ld, nchw, B, C, (int64_t)H * W);
-  else if (dtype == RDST_BF16) hipLaunchKernelGGL((rows_to_nchw_kernel<bf16>), grid, dim3(256), 0, st, (const bf16*)rows, ld, nchw, B, C, (int64_t)H * W);
-  else return rdst_fail(RDST_EINVAL, "rdst_rows_to_nchw: bad dtype %d", dtype);
+  else hipLaunchKernelGGL((rows_to_nchw_kernel<bf16>), grid, dim3(256), 0, st, (const bf16*)rows, ld, nchw, B, C, (int64_t)H * W);
   return rdst_launch_status("rows_to_nchw");
 }

@@ -461,25 +461,28 @@ size_t conv3_pack_bytes(int Cin, int Cout) {
   return (f > d ? f : d) + 256;
 }
 
+int conv3_fwd_shape(int Cin, int Cout, int ks, int r, bool has_res, int in_act) {
+  if (ks != 3 || in_act) return 0;
+  if (Cin == 150 && Cout == 60 && r == 1) return 1;
+  if (Cin == 60 && Cout == 60 && r == 1) return 2;
+  if (Cin == 60 && Cout == 240 && r == 2 && !has_res) return 3;
+  return 0;
+}
+
 // Forward.  RDST_ENOTSUP = not one of the covered shapes (the caller falls back to conv_mfma.hip).
 int conv3_fwd_bf16(const bf16* X, int64_t ldx, int in_act, const float* Wc, const float* bias, const bf16* R, int64_t ldr,
                    bf16* Y, int64_t ldy, const ConvGeom& g, float s, void* wpack, bool prepacked, hipStream_t st) {
-  if (!wpack || g.ks != 3 || g.pad != 1 || in_act || g.W % 32 || ((uintptr_t)wpack & 15)) return RDST_ENOTSUP;
-  const bool ps = g.r == 2;
-  if (!(g.r == 1 || (ps && !R))) return RDST_ENOTSUP;
+  if (!wpack || g.pad != 1 || g.W % 32 || ((uintptr_t)wpack & 15)) return RDST_ENOTSUP;
+  const int shape = conv3_fwd_shape(g.Cin, g.Cout, g.ks, g.r, R != nullptr, in_act);
+  if (!shape) return RDST_ENOTSUP;
   const int cy = g.Cout / (g.r * g.r);
   if (!rows_aligned(X, ldx) || !rows_aligned(Y, ldy) || (R && !rows_aligned(R, ldr)) || (cy & 1)) return RDST_ENOTSUP;
-  int shape = 0;
-  if (g.Cin == 150 && g.Cout == 60 && !ps) shape = 1;
-  else if (g.Cin == 60 && g.Cout == 60 && !ps) shape = 2;
-  else if (g.Cin == 60 && g.Cout == 240 && ps) shape = 3;
-  if (!shape) return RDST_ENOTSUP;
-  bf16* wp = reinterpret_cast<bf16*>(wpack);
-  if (!prepacked)
-    if (int rc = pack(Wc, wp, g.Cin, g.Cout, g.Cin, g.Cout, PK_FWD, s, st)) return rc;
   const int64_t abytes = ((g.pixels() - 1) * ldx + g.Cin) * 2;
   const int64_t opix = g.pixels() * g.r * g.r;
   if (abytes >= (1ll << 31) || opix * ldy * 2 >= (1ll << 31) || (R && opix * ldr * 2 >= (1ll << 31))) return RDST_ENOTSUP;
+  bf16* wp = reinterpret_cast<bf16*>(wpack);
+  if (!prepacked)
+    if (int rc = pack(Wc, wp, g.Cin, g.Cout, g.Cin, g.Cout, PK_FWD, s, st)) return rc;
   C3Args p{};
   p.A = X; p.lda = ldx; p.a_bytes = (int)abytes; p.Wp = wp; p.bias = bias; p.R = R; p.ldr = ldr; p.Y = Y; p.ldy = ldy;
   p.B = g.B; p.H = g.H; p.W = g.W; p.N = g.Cout; p.s = s;

@@ -493,12 +493,12 @@ int conv3x_fwd_f32(const float* X, int64_t ldx, int in_act, const float* Wc, con
   const int shape = conv3x_fwd_shape(g.Cin, g.Cout, g.ks, g.r, R != nullptr, in_act);
   if (!shape) return RDST_ENOTSUP;
   if (!rows_aligned(X) || !rows_aligned(Y) || (R && !rows_aligned(R))) return RDST_ENOTSUP;
-  uint32_t* wp = reinterpret_cast<uint32_t*>(wpack);
-  if (!prepacked)
-    if (int rc = pack(Wc, wp, g.Cin, g.Cout, g.Cin, g.Cout, PK_FWD, s, st)) return rc;
   const int64_t abytes = ((g.pixels() - 1) * ldx + g.Cin) * 4;
   const int64_t opix = g.pixels() * g.r * g.r;
   if (abytes >= (1ll << 31) || opix * ldy * 4 >= (1ll << 31) || (R && opix * ldr * 4 >= (1ll << 31))) return RDST_ENOTSUP;
+  uint32_t* wp = reinterpret_cast<uint32_t*>(wpack);
+  if (!prepacked)
+    if (int rc = pack(Wc, wp, g.Cin, g.Cout, g.Cin, g.Cout, PK_FWD, s, st)) return rc;
   C3Args p{};
   p.A = X; p.lda = ldx; p.a_bytes = (int)abytes; p.Wp = wp; p.bias = bias; p.R = R; p.ldr = ldr; p.Y = Y; p.ldy = ldy;
   p.B = g.B; p.H = g.H; p.W = g.W; p.N = g.Cout; p.s = s; p.ymul = 1; p.xmul = 1;

@@ -491,7 +491,7 @@ __global__ void __launch_bounds__(512) conv_rows_kernel(const ConvArgs<T> p) {
 // row-stripe kernel: 3x3 / pad 1, W % 32 == 0, PixelShuffle factor 1 or 2 (2: forward, no residual),
 // dword-aligned rows of at least 16 B whose last 128-B chunk is not shorter than 16 B
 template <typename T, int MODE>
-int launch_conv_rows(ConvArgs<T>& p, hipStream_t st, const char* what) {
+int launch_conv_rows(ConvArgs<T>& p, bool split, hipStream_t st, const char* what) {
   using MM = Mma<T>;
   const ConvGeom& g = p.g;
   if (g.ks != 3 || g.pad != 1 || g.W % 32 != 0 || rdst_dbg_getenv("RDST_CONV_V1")) return RDST_ENOTSUP;
@@ -519,17 +519,17 @@ int launch_conv_rows(ConvArgs<T>& p, hipStream_t st, const char* what) {
   if (pf < 0) { const char* e = rdst_dbg_getenv("RDST_CONV_PF"); pf = e ? atoi(e) : 3; }
   auto kern = pf == 1 ? conv_rows_kernel<T, MODE, 1> : pf == 2 ? conv_rows_kernel<T, MODE, 2> : conv_rows_kernel<T, MODE, 3>;
   if constexpr (sizeof(T) == 4)
-    if (rdst_split()) kern = pf == 1 ? conv_rows_kernel<T, MODE, 1, true> : pf == 2 ? conv_rows_kernel<T, MODE, 2, true> : conv_rows_kernel<T, MODE, 3, true>;
+    if (split) kern = pf == 1 ? conv_rows_kernel<T, MODE, 1, true> : pf == 2 ? conv_rows_kernel<T, MODE, 2, true> : conv_rows_kernel<T, MODE, 3, true>;
   if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, st, p);
   return rdst_launch_status(what);
 }
 
 template <typename T, int MODE>
-int launch_conv(ConvArgs<T>& p, hipStream_t st, const char* what) {
+int launch_conv(ConvArgs<T>& p, bool split, hipStream_t st, const char* what) {
   using MM = Mma<T>;
   {
-    const int rc = launch_conv_rows<T, MODE>(p, st, what);
+    const int rc = launch_conv_rows<T, MODE>(p, split, st, what);
     if (rc != RDST_ENOTSUP) return rc;
   }
   p.Tn = (p.CA + MM::KP - 1) / MM::KP;
@@ -556,7 +556,7 @@ int launch_conv(ConvArgs<T>& p, hipStream_t st, const char* what) {
   {                                                                                                                  \
     auto kern = conv_mfma_kernel<T, TM, MODE>;                                                                       \
     if constexpr (sizeof(T) == 4)                                                                                    \
-      if (rdst_split()) kern = conv_mfma_kernel<T, TM, MODE, true>;                                                  \
+      if (split) kern = conv_mfma_kernel<T, TM, MODE, true>;                                                         \
     if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, st, p);                                          \
   }
@@ -1108,7 +1108,7 @@ __global__ void __launch_bounds__(256) conv_wgrad_reduce_kernel(const float* __r
 
 template <typename T>
 int conv_fwd_mfma(const T* X, int64_t ldx, int in_act, const float* Wc, const float* bias, const T* R, int64_t ldr,
-                  T* Y, int64_t ldy, const ConvGeom& g, float s, hipStream_t st) {
+                  T* Y, int64_t ldy, const ConvGeom& g, float s, bool split, hipStream_t st) {
   if (mfma_disabled() || !rows_ok<T>(X, ldx) || g.Cin < 8) return RDST_ENOTSUP;
   // fp32: the weights of all taps stay in LDS and a wave holds the contracted channels of its pixels as <= 16 k-steps of 8:
   // more than 128 input channels (the 150 -> 60 fusion conv of an RDSTB) run as launches over equal slices of the input
@@ -1121,7 +1121,7 @@ int conv_fwd_mfma(const T* X, int64_t ldx, int in_act, const float* Wc, const fl
     p.A = X + i * cs; p.lda = ldx; p.CA = cs; p.Wc = Wc + (int64_t)i * cs * g.ks * g.ks;
     p.bias = i == 0 ? bias : nullptr; p.R = i == 0 ? R : Y; p.ldr = i == 0 ? ldr : ldy; p.Y = Y; p.ldy = ldy;
     p.in_act = in_act; p.g = g; p.Nout = g.Cout; p.s = s;
-    const int rc = launch_conv<T, CMODE_FWD>(p, st, "conv_fwd_mfma");
+    const int rc = launch_conv<T, CMODE_FWD>(p, split, st, "conv_fwd_mfma");
     if (rc == RDST_ENOTSUP && i > 0) return rdst_fail(RDST_EINVAL, "conv_fwd_mfma: slice %d of %d declined after slice 0 ran", i, nsl);
     if (rc) return rc;
   }
@@ -1160,7 +1160,7 @@ const T* plain_dy(const T* dY, int64_t lddy, const ConvGeom& g, void* scratch, i
 
 template <typename T>
 int conv_dgrad_mfma(const T* X, int64_t ldx, int in_act, const float* Wc, const T* dYp, int64_t lddyp, T* dX,
-                    int64_t lddx, const T* acc, int64_t ldacc, const ConvGeom& g, float s, hipStream_t st) {
+                    int64_t lddx, const T* acc, int64_t ldacc, const ConvGeom& g, float s, bool split, hipStream_t st) {
   // dYp must already be plain rows (B*H*W, Cout)
   if (mfma_disabled() || !rows_ok<T>(dYp, lddyp) || g.Cout < 8) return RDST_ENOTSUP;
   // fp32, more than 128 output channels (the 60 -> 240 convs of the upsampler): launches over slices of the output
@@ -1176,7 +1176,7 @@ int conv_dgrad_mfma(const T* X, int64_t ldx, int in_act, const float* Wc, const 
     p.A = dYp + i * cs; p.lda = lddyp; p.CA = cs; p.Wc = Wc + (int64_t)i * cs * g.Cin * g.ks * g.ks;
     p.Y = dX; p.ldy = lddx; p.Xa = X; p.ldxa = ldx;
     p.in_act = in_act; p.Acc = i == 0 ? acc : dX; p.ldacc = i == 0 ? ldacc : lddx; p.g = g; p.Nout = g.Cin; p.s = s;
-    const int rc = launch_conv<T, CMODE_DGRAD>(p, st, "conv_dgrad_mfma");
+    const int rc = launch_conv<T, CMODE_DGRAD>(p, split, st, "conv_dgrad_mfma");
     if (rc == RDST_ENOTSUP && i > 0) return rdst_fail(RDST_EINVAL, "conv_dgrad_mfma: slice %d of %d declined after slice 0 ran", i, nsl);
     if (rc) return rc;
   }
@@ -1185,7 +1185,7 @@ int conv_dgrad_mfma(const T* X, int64_t ldx, int in_act, const float* Wc, const 
 
 template <typename T>
 int conv_wgrad_mfma(const T* X, int64_t ldx, int in_act, const T* dYp, int64_t lddyp, float* dW, float* dbias,
-                    float* slab, const ConvGeom& g, float s, hipStream_t st) {
+                    float* slab, const ConvGeom& g, float s, bool split, hipStream_t st) {
   if (mfma_disabled() || !rows_ok<T>(X, ldx) || !rows_ok<T>(dYp, lddyp)) return RDST_ENOTSUP;
   ConvWgradArgs<T> p{};
   p.X = X; p.ldx = ldx; p.in_act = in_act; p.dY = dYp; p.lddy = lddyp; p.slab = slab; p.g = g;
@@ -1195,9 +1195,7 @@ int conv_wgrad_mfma(const T* X, int64_t ldx, int in_act, const T* dYp, int64_t l
   p.ones_col = g.Cin;
   if (p.NT * g.ks * p.KT > 8 * CW_MAXT) return RDST_ENOTSUP;
   // RDST_F32X3: the pipelined kernel's split form
-  bool split = false;
-  if constexpr (sizeof(T) == 4)
-    split = rdst_split() && g.ks == 3 && g.pad == 1 && g.W % CW_STRIPE == 0;
+  split = sizeof(T) == 4 && split && g.ks == 3 && g.pad == 1 && g.W % CW_STRIPE == 0;
   auto stride = [split](int elems) {   // (split mode: two bf16 planes in the bytes of the fp32 row, read like bf16 rows)
     const int b = elems * (int)sizeof(T);
     if (sizeof(T) == 4 && !split) return b;
@@ -1260,11 +1258,11 @@ int conv_wgrad_mfma(const T* X, int64_t ldx, int in_act, const T* dYp, int64_t l
 
 #define INST(T)                                                                                                       \
   template int conv_fwd_mfma<T>(const T*, int64_t, int, const float*, const float*, const T*, int64_t, T*, int64_t,  \
-                                const ConvGeom&, float, hipStream_t);                                                \
+                                const ConvGeom&, float, bool, hipStream_t);                                          \
   template int conv_dgrad_mfma<T>(const T*, int64_t, int, const float*, const T*, int64_t, T*, int64_t, const T*,    \
-                                  int64_t, const ConvGeom&, float, hipStream_t);                                     \
+                                  int64_t, const ConvGeom&, float, bool, hipStream_t);                               \
   template int conv_wgrad_mfma<T>(const T*, int64_t, int, const T*, int64_t, float*, float*, float*, const ConvGeom&, \
-                                  float, hipStream_t);                                                               \
+                                  float, bool, hipStream_t);                                                         \
   template const T* plain_dy<T>(const T*, int64_t, const ConvGeom&, void*, int64_t&, hipStream_t, int&);
 INST(float)
 INST(bf16)

@@ -342,16 +342,20 @@ size_t lin3_pack_bytes(int K, int N) {
 }
 
 // RDST_ENOTSUP = not one of the covered shapes (the caller falls back to linear_mfma.hip)
+// 1 qkv (LN, N = 3K), 2 proj (residual, N = K), 3 dense tail (LN, N = 30); 0 = not covered
+int lin3_kind(int K, int N, bool ln, bool res, int in_act) {
+  if (in_act || !(K == 60 || K == 90 || K == 120)) return 0;
+  if (ln && !res && N == 3 * K) return 1;
+  if (!ln && res && N == K) return 2;
+  if (ln && !res && N == 30) return 3;
+  return 0;
+}
+
 int lin3_fwd_bf16(const bf16* X, int64_t ldx, const float* ln_w, const float* ln_b, int in_act, const float* Wt, const float* bias,
                   const bf16* R, int64_t ldr, bf16* Y, int64_t ldy, float* stats, int64_t M, int K, int N, float s, void* wpack,
                   bool prepacked, hipStream_t st) {
-  if (!wpack || ((uintptr_t)wpack & 15) || in_act || !Wt || M <= 0) return RDST_ENOTSUP;
-  const bool ln = ln_w != nullptr;
-  if (!(K == 60 || K == 90 || K == 120)) return RDST_ENOTSUP;
-  int kind = 0;   // 1 qkv (LN, N = 3K), 2 proj (residual, N = K), 3 dense tail (LN, N = 30)
-  if (ln && !R && N == 3 * K) kind = 1;
-  else if (!ln && R && N == K) kind = 2;
-  else if (ln && !R && N == 30) kind = 3;
+  if (!wpack || ((uintptr_t)wpack & 15) || !Wt || M <= 0) return RDST_ENOTSUP;
+  const int kind = lin3_kind(K, N, ln_w != nullptr, R != nullptr, in_act);
   if (!kind) return RDST_ENOTSUP;
   if (((uintptr_t)X & 3) || (ldx & 1) || ((uintptr_t)Y & 3) || (ldy & 1) || (R && (((uintptr_t)R & 3) || (ldr & 1)))) return RDST_ENOTSUP;
   const int64_t xb = ((M - 1) * ldx + K) * 2;

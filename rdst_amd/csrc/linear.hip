@@ -429,7 +429,7 @@ size_t slab_floats(int64_t M, int K, int N) {
 
 template <typename T>
 int fwd_t(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, int in_act, const float* Wt, const float* bias,
-          const T* R, int64_t ldr, T* Y, int64_t ldy, float* stats, int64_t M, int K, int N, float s, hipStream_t st) {
+          const T* R, int64_t ldr, T* Y, int64_t ldy, float* stats, int64_t M, int K, int N, float s, bool split, hipStream_t st) {
   auto run_stats = [&]() -> int {
     hipLaunchKernelGGL((row_stats_kernel<T>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, X, ldx, stats, M, K);
     return rdst_launch_status("row_stats");
@@ -448,7 +448,7 @@ int fwd_t(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, int in_
     return rdst_launch_status("ln_apply");
   }
   // the MFMA path computes (and stores) the LayerNorm statistics itself
-  if (int rc = linear_fwd_mfma<T>(X, ldx, ln_w, ln_b, in_act, Wt, bias, R, ldr, Y, ldy, stats, M, K, N, s, st);
+  if (int rc = linear_fwd_mfma<T>(X, ldx, ln_w, ln_b, in_act, Wt, bias, R, ldr, Y, ldy, stats, M, K, N, s, split, st);
       rc != RDST_ENOTSUP)
     return rc;
   if (ln_w)
@@ -463,13 +463,13 @@ template <typename T>
 int bwd_t(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, const float* stats, int in_act, const float* Wt,
           const T* dY, int64_t lddy, T* dX, int64_t lddx, const T* acc, int64_t ldacc, float* dW, float* dbias,
           float* dln_w,
-          float* dln_b, float* wsp, int64_t M, int K, int N, float s, hipStream_t st, const T* acc2 = nullptr, int64_t ldacc2 = 0) {
+          float* dln_b, float* wsp, int64_t M, int K, int N, float s, bool split, hipStream_t st, const T* acc2, int64_t ldacc2) {
   // workspace carve: [dA: M*K] [slabW: splits*N*K] [small: kSmallBlocks * max(N, 2K)]
   float* dA = wsp;
   float* slabW = dA + (ln_w ? M * K : 0);
   float* small = slabW + slab_floats(M, K, N);
   if constexpr (sizeof(T) == 4) {   // RDST_F32X3: the one-pass kernel of the E1 shapes (every gradient requested), else the paths below
-    if (rdst_split() && Wt && dX && dW && dbias && (!ln_w || (dln_w && dln_b && (int64_t)N * (K + 1) <= M * K)) && !rdst_dbg_getenv("RDST_LBX_OFF")) {
+    if (split && Wt && dX && dW && dbias && (!ln_w || (dln_w && dln_b && (int64_t)N * (K + 1) <= M * K)) && !rdst_dbg_getenv("RDST_LBX_OFF")) {
       const int rc = lnlin3x_bwd_f32(X, ldx, ln_w, ln_b, stats, in_act, Wt, dY, lddy, dX, lddx, acc, ldacc, acc2, ldacc2, dW, dbias, dln_w,
                                      dln_b, slabW, dA, M, K, N, s, st);
       if (rc != RDST_ENOTSUP) return rc;
@@ -496,9 +496,9 @@ int bwd_t(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, const f
           if (rcf != RDST_ENOTSUP) return rcf;
         }
         int rc = linear_wgrad_ln_mfma<T>(X, ldx, ln_w, ln_b, stats, Wt, dY, lddy, dW, dbias, dln_w, dln_b, slabW, G, M, K, N,
-                                         s, st);
+                                         s, split, st);
         if (rc == 0) {
-          rc = linear_dgrad_ln2_mfma<T>(X, ldx, stats, ln_w, Wt, dY, lddy, dX, lddx, acc, ldacc, M, K, N, s, st);
+          rc = linear_dgrad_ln2_mfma<T>(X, ldx, stats, ln_w, Wt, dY, lddy, dX, lddx, acc, ldacc, M, K, N, s, split, st);
           if (rc == 0) return 0;
           if (rc != RDST_ENOTSUP) return rc;
           if (N >= 64) {
@@ -507,9 +507,9 @@ int bwd_t(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, const f
             // output features, the second accumulating onto the first (in place), replace the scalar GEMM + LayerNorm-backward
             // pair this shape used to fall back to
             const int N1 = (N / 2 + 3) / 4 * 4;
-            rc = linear_dgrad_ln2_mfma<T>(X, ldx, stats, ln_w, Wt, dY, lddy, dX, lddx, acc, ldacc, M, K, N1, s, st);
+            rc = linear_dgrad_ln2_mfma<T>(X, ldx, stats, ln_w, Wt, dY, lddy, dX, lddx, acc, ldacc, M, K, N1, s, split, st);
             if (rc == 0) {
-              rc = linear_dgrad_ln2_mfma<T>(X, ldx, stats, ln_w, Wt + (int64_t)N1 * K, dY + N1, lddy, dX, lddx, dX, lddx, M, K, N - N1, s, st);
+              rc = linear_dgrad_ln2_mfma<T>(X, ldx, stats, ln_w, Wt + (int64_t)N1 * K, dY + N1, lddy, dX, lddx, dX, lddx, M, K, N - N1, s, split, st);
               if (rc != RDST_ENOTSUP) return rc;   // (a refused SECOND half leaves dX half done: rebuilt from scratch below)
             } else if (rc != RDST_ENOTSUP) {
               return rc;
@@ -531,7 +531,7 @@ int bwd_t(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, const f
     }
     bool wgrad_done = false;
     if (dW || dbias) {
-      const int rc = linear_wgrad_mfma<T>(X, ldx, ln_w, ln_b, stats, in_act, dY, lddy, dW, dbias, slabW, M, K, N, s, st);
+      const int rc = linear_wgrad_mfma<T>(X, ldx, ln_w, ln_b, stats, in_act, dY, lddy, dW, dbias, slabW, M, K, N, s, split, st);
       if (rc == 0) wgrad_done = true;
       else if (rc != RDST_ENOTSUP) return rc;
     }
@@ -557,7 +557,7 @@ int bwd_t(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, const f
       if (rc != RDST_ENOTSUP) return rc;
     }
     if (dX) {
-      int rc = linear_dgrad_mfma<T>(X, ldx, ln_w != nullptr, in_act, Wt, dY, lddy, dX, lddx, acc, ldacc, dA, M, K, N, s, st);
+      int rc = linear_dgrad_mfma<T>(X, ldx, ln_w != nullptr, in_act, Wt, dY, lddy, dX, lddx, acc, ldacc, dA, M, K, N, s, split, st);
       if (rc == RDST_ENOTSUP) {
         DyA<T> la{dY, lddy, s};
         WtBT lb{Wt, K};
@@ -631,10 +631,10 @@ int ln_only_bwd(const T* X, int64_t ldx, const float* ln_w, const float* stats, 
 }  // namespace
 
 extern "C" int rdst_ln_linear_fwd_packable(int K, int N, int has_ln, int has_residual, int in_act, int dtype) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
-  if (dtype == RDST_F32 && rdst_split()) return lin3x_kind(K, N, has_ln != 0, has_residual != 0, in_act) != 0;   // lin3x_mfma.hip
-  if (dtype != RDST_BF16 || in_act || !(K == 60 || K == 90 || K == 120)) return 0;
-  return (has_ln && !has_residual && (N == 3 * K || N == 30)) || (!has_ln && has_residual && N == K);
+  bool split;
+  if (rdst_dtype(dtype, split, "rdst_ln_linear_fwd_packable")) return 0;
+  if (split) return lin3x_kind(K, N, has_ln != 0, has_residual != 0, in_act) != 0;   // lin3x_mfma.hip
+  return dtype == RDST_BF16 && lin3_kind(K, N, has_ln != 0, has_residual != 0, in_act) != 0;   // lin3_mfma.hip
 }
 
 extern "C" size_t rdst_ln_linear_fwd_workspace(int K, int N) {
@@ -652,7 +652,8 @@ extern "C" int rdst_ln_linear_fwd(const void* X, int64_t ld_x, const float* ln_w
                                   const float* Wt, const float* bias, const void* R, int64_t ld_r, void* Y, int64_t ld_y,
                                   float* stats, void* workspace, size_t workspace_bytes, int64_t M, int K, int N,
                                   float out_scale, int dtype, void* stream) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
+  bool split;
+  if (int rc = rdst_dtype(dtype, split, "rdst_ln_linear_fwd")) return rc;
   if (!X || !Y) return rdst_fail(RDST_EINVAL, "rdst_ln_linear_fwd: null pointer");
   if (M < 0 || K <= 0 || N <= 0) return rdst_fail(RDST_EINVAL, "rdst_ln_linear_fwd: bad dimensions");
   if ((ln_w == nullptr) != (ln_b == nullptr)) return rdst_fail(RDST_EINVAL, "rdst_ln_linear_fwd: ln_w/ln_b must come together");
@@ -660,7 +661,6 @@ extern "C" int rdst_ln_linear_fwd(const void* X, int64_t ld_x, const float* ln_w
   if (ln_w && in_act) return rdst_fail(RDST_EINVAL, "rdst_ln_linear_fwd: LayerNorm and in_act are exclusive");
   if (!Wt && (!ln_w || N != K)) return rdst_fail(RDST_EINVAL, "rdst_ln_linear_fwd: Wt == NULL means LayerNorm only (N == K)");
   if (ld_x < K || ld_y < N || (R && ld_r < N)) return rdst_fail(RDST_EINVAL, "rdst_ln_linear_fwd: leading dimension too small");
-  if (dtype != RDST_F32 && dtype != RDST_BF16) return rdst_fail(RDST_EINVAL, "rdst_ln_linear_fwd: bad dtype %d", dtype);
   if (M == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   if (dtype == RDST_BF16 && workspace && workspace_bytes >= rdst_ln_linear_fwd_workspace(K, N)) {
@@ -668,14 +668,14 @@ extern "C" int rdst_ln_linear_fwd(const void* X, int64_t ld_x, const float* ln_w
                                  K, N, out_scale, workspace, workspace_bytes == RDST_PREPACKED, st);
     if (rc != RDST_ENOTSUP) return rc;   // (a prepacked image the call cannot use is simply ignored)
   }
-  if (dtype == RDST_F32 && rdst_split() && workspace && workspace_bytes >= lin3x_pack_bytes(K, N)) {
+  if (split && workspace && workspace_bytes >= lin3x_pack_bytes(K, N)) {
     const int rc = lin3x_fwd_f32((const float*)X, ld_x, ln_w, ln_b, in_act, Wt, bias, (const float*)R, ld_r, (float*)Y, ld_y, stats, M,
                                  K, N, out_scale, workspace, workspace_bytes == RDST_PREPACKED, st);
     if (rc != RDST_ENOTSUP) return rc;
   }
   if (dtype == RDST_F32)
-    return fwd_t<float>((const float*)X, ld_x, ln_w, ln_b, in_act, Wt, bias, (const float*)R, ld_r, (float*)Y, ld_y, stats, M, K, N, out_scale, st);
-  return fwd_t<bf16>((const bf16*)X, ld_x, ln_w, ln_b, in_act, Wt, bias, (const bf16*)R, ld_r, (bf16*)Y, ld_y, stats, M, K, N, out_scale, st);
+    return fwd_t<float>((const float*)X, ld_x, ln_w, ln_b, in_act, Wt, bias, (const float*)R, ld_r, (float*)Y, ld_y, stats, M, K, N, out_scale, split, st);
+  return fwd_t<bf16>((const bf16*)X, ld_x, ln_w, ln_b, in_act, Wt, bias, (const bf16*)R, ld_r, (bf16*)Y, ld_y, stats, M, K, N, out_scale, false, st);
 }
 
 extern "C" size_t rdst_ln_linear_bwd_workspace(int64_t M, int K, int N) {
@@ -684,34 +684,44 @@ extern "C" size_t rdst_ln_linear_bwd_workspace(int64_t M, int K, int N) {
   return sizeof(float) * ((size_t)M * K + slab_floats(M, K, N) + (size_t)kSmallBlocks * mx + 2 * (size_t)K + 64);
 }
 
-extern "C" int rdst_ln_linear_bwd2(const void* X, int64_t ld_x, const float* ln_w, const float* ln_b, const float* stats,
-                                  int in_act, const float* Wt, const void* dY, int64_t ld_dy, void* dX, int64_t ld_dx,
-                                  const void* dX_add, int64_t ld_dx_add, float* dW, float* dbias, float* dln_w, float* dln_b,
-                                  void* workspace,
-                                  size_t workspace_bytes, int64_t M, int K, int N, float out_scale, int dtype,
-                                  void* stream, const void* dX_add2, int64_t ld_dx_add2) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
+namespace {
+// rdst_ln_linear_bwd / rdst_ln_linear_bwd2 after the dtype is decoded
+int ln_linear_bwd(const void* X, int64_t ld_x, const float* ln_w, const float* ln_b, const float* stats, int in_act, const float* Wt,
+                  const void* dY, int64_t ld_dy, void* dX, int64_t ld_dx, const void* dX_add, int64_t ld_dx_add, float* dW, float* dbias,
+                  float* dln_w, float* dln_b, void* workspace, size_t workspace_bytes, int64_t M, int K, int N, float out_scale,
+                  int dtype, bool split, hipStream_t st, const void* dX_add2, int64_t ld_dx_add2) {
   if (!X || !dY || !workspace) return rdst_fail(RDST_EINVAL, "rdst_ln_linear_bwd: null pointer");
   if (M < 0 || K <= 0 || N <= 0) return rdst_fail(RDST_EINVAL, "rdst_ln_linear_bwd: bad dimensions");
   if (ln_w && !stats) return rdst_fail(RDST_EINVAL, "rdst_ln_linear_bwd: LayerNorm needs the forward's stats");
   if (!Wt && (!ln_w || N != K)) return rdst_fail(RDST_EINVAL, "rdst_ln_linear_bwd: Wt == NULL means LayerNorm only (N == K)");
   if (ld_x < K || ld_dy < N || (dX && ld_dx < K)) return rdst_fail(RDST_EINVAL, "rdst_ln_linear_bwd: leading dimension too small");
-  if (dtype != RDST_F32 && dtype != RDST_BF16) return rdst_fail(RDST_EINVAL, "rdst_ln_linear_bwd: bad dtype %d", dtype);
   if (workspace_bytes < rdst_ln_linear_bwd_workspace(M, K, N)) return rdst_fail(RDST_EINVAL, "rdst_ln_linear_bwd: workspace too small");
   if (M == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
   float* wsp = (float*)workspace;
-  if (dX_add2 && (!Wt || (dtype != RDST_BF16 && !(dtype == RDST_F32 && rdst_split() && lnlin3x_bwd_kind(K, N, ln_w != nullptr, in_act))))) return RDST_ENOTSUP;
+  if (dX_add2 && (!Wt || (dtype != RDST_BF16 && !(split && lnlin3x_bwd_kind(K, N, ln_w != nullptr, in_act))))) return RDST_ENOTSUP;
   if (!Wt) {
     if (dtype == RDST_F32)
       return ln_only_bwd<float>((const float*)X, ld_x, ln_w, stats, (const float*)dY, ld_dy, (float*)dX, ld_dx, (const float*)dX_add, ld_dx_add, dln_w, dln_b, wsp, M, K, out_scale, st);
     return ln_only_bwd<bf16>((const bf16*)X, ld_x, ln_w, stats, (const bf16*)dY, ld_dy, (bf16*)dX, ld_dx, (const bf16*)dX_add, ld_dx_add, dln_w, dln_b, wsp, M, K, out_scale, st);
   }
   if (dtype == RDST_F32)
-    return bwd_t<float>((const float*)X, ld_x, ln_w, ln_b, stats, in_act, Wt, (const float*)dY, ld_dy, (float*)dX, ld_dx, (const float*)dX_add, ld_dx_add, dW, dbias, dln_w, dln_b, wsp, M, K, N, out_scale, st,
+    return bwd_t<float>((const float*)X, ld_x, ln_w, ln_b, stats, in_act, Wt, (const float*)dY, ld_dy, (float*)dX, ld_dx, (const float*)dX_add, ld_dx_add, dW, dbias, dln_w, dln_b, wsp, M, K, N, out_scale, split, st,
                       (const float*)dX_add2, ld_dx_add2);
-  return bwd_t<bf16>((const bf16*)X, ld_x, ln_w, ln_b, stats, in_act, Wt, (const bf16*)dY, ld_dy, (bf16*)dX, ld_dx, (const bf16*)dX_add, ld_dx_add, dW, dbias, dln_w, dln_b, wsp, M, K, N, out_scale, st,
+  return bwd_t<bf16>((const bf16*)X, ld_x, ln_w, ln_b, stats, in_act, Wt, (const bf16*)dY, ld_dy, (bf16*)dX, ld_dx, (const bf16*)dX_add, ld_dx_add, dW, dbias, dln_w, dln_b, wsp, M, K, N, out_scale, false, st,
                      (const bf16*)dX_add2, ld_dx_add2);
+}
+}  // namespace
+
+extern "C" int rdst_ln_linear_bwd2(const void* X, int64_t ld_x, const float* ln_w, const float* ln_b, const float* stats,
+                                  int in_act, const float* Wt, const void* dY, int64_t ld_dy, void* dX, int64_t ld_dx,
+                                  const void* dX_add, int64_t ld_dx_add, float* dW, float* dbias, float* dln_w, float* dln_b,
+                                  void* workspace,
+                                  size_t workspace_bytes, int64_t M, int K, int N, float out_scale, int dtype,
+                                  void* stream, const void* dX_add2, int64_t ld_dx_add2) {
+  bool split;
+  if (int rc = rdst_dtype(dtype, split, "rdst_ln_linear_bwd")) return rc;
+  return ln_linear_bwd(X, ld_x, ln_w, ln_b, stats, in_act, Wt, dY, ld_dy, dX, ld_dx, dX_add, ld_dx_add, dW, dbias, dln_w, dln_b, workspace,
+                       workspace_bytes, M, K, N, out_scale, dtype, split, (hipStream_t)stream, dX_add2, ld_dx_add2);
 }
 
 extern "C" int rdst_ln_linear_bwd(const void* X, int64_t ld_x, const float* ln_w, const float* ln_b, const float* stats,
@@ -719,7 +729,8 @@ extern "C" int rdst_ln_linear_bwd(const void* X, int64_t ld_x, const float* ln_w
                                   const void* dX_add, int64_t ld_dx_add, float* dW, float* dbias, float* dln_w, float* dln_b,
                                   void* workspace, size_t workspace_bytes, int64_t M, int K, int N, float out_scale, int dtype,
                                   void* stream) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
-  return rdst_ln_linear_bwd2(X, ld_x, ln_w, ln_b, stats, in_act, Wt, dY, ld_dy, dX, ld_dx, dX_add, ld_dx_add, dW, dbias, dln_w, dln_b,
-                             workspace, workspace_bytes, M, K, N, out_scale, dtype, stream, nullptr, 0);
+  bool split;
+  if (int rc = rdst_dtype(dtype, split, "rdst_ln_linear_bwd")) return rc;
+  return ln_linear_bwd(X, ld_x, ln_w, ln_b, stats, in_act, Wt, dY, ld_dy, dX, ld_dx, dX_add, ld_dx_add, dW, dbias, dln_w, dln_b, workspace,
+                       workspace_bytes, M, K, N, out_scale, dtype, split, (hipStream_t)stream, nullptr, 0);
 }

@@ -717,7 +717,7 @@ __global__ void __launch_bounds__(512) lin_dgrad_ln_kernel(const LnDgradArgs<T> 
 }
 
 template <typename T, int MODE>
-int launch_lin(LinArgs<T>& p, hipStream_t st, const char* what) {
+int launch_lin(LinArgs<T>& p, bool split, hipStream_t st, const char* what) {
   using MM = Mma<T>;
   p.Tn = (p.Kc + MM::KP - 1) / MM::KP;
   if (p.Tn > 32) return RDST_ENOTSUP;
@@ -763,7 +763,7 @@ int launch_lin(LinArgs<T>& p, hipStream_t st, const char* what) {
   {                                                                                                                  \
     auto kern = lin_mfma_kernel<T, TM, MODE>;                                                                        \
     if constexpr (sizeof(T) == 4)                                                                                    \
-      if (rdst_split()) kern = lin_mfma_kernel<T, TM, MODE, true>;                                                   \
+      if (split) kern = lin_mfma_kernel<T, TM, MODE, true>;                                                          \
     if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, st, p);                                          \
   }
@@ -1351,24 +1351,24 @@ int wgrad_ln_finish_launch(const float* G, const float* Wt, const float* ln_w, c
 template <typename T>
 int linear_fwd_mfma(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, int in_act, const float* Wt,
                     const float* bias, const T* R, int64_t ldr, T* Y, int64_t ldy, float* stats, int64_t M, int K,
-                    int N, float s, hipStream_t st) {
+                    int N, float s, bool split, hipStream_t st) {
   if (mfma_disabled() || !rows_ok<T>(X, ldx)) return RDST_ENOTSUP;
   LinArgs<T> p{};
   p.A = X; p.lda = ldx; p.lnw = ln_w; p.lnb = ln_b; p.in_act = in_act; p.Wt = Wt; p.wK = K; p.bias = bias;
   p.R = R; p.ldr = ldr; p.Y = Y; p.ldy = ldy; p.stats = stats; p.M = M; p.Kc = K; p.Nout = N; p.s = s;
-  return launch_lin<T, MODE_FWD>(p, st, "lin_fwd_mfma");
+  return launch_lin<T, MODE_FWD>(p, split, st, "lin_fwd_mfma");
 }
 
 template <typename T>
 int linear_dgrad_mfma(const T* X, int64_t ldx, bool has_ln, int in_act, const float* Wt, const T* dY, int64_t lddy,
                       T* dX, int64_t lddx, const T* acc, int64_t ldacc, float* dA, int64_t M, int K, int N, float s,
-                      hipStream_t st) {
+                      bool split, hipStream_t st) {
   if (mfma_disabled() || !rows_ok<T>(dY, lddy)) return RDST_ENOTSUP;
   LinArgs<T> p{};
   p.A = dY; p.lda = lddy; p.in_act = in_act; p.Wt = Wt; p.wK = K; p.Y = dX; p.ldy = lddx;
   p.dA = has_ln ? dA : nullptr; p.Xa = X; p.ldxa = ldx; p.Acc = acc; p.ldacc = ldacc;
   p.M = M; p.Kc = N; p.Nout = K; p.s = s;
-  return launch_lin<T, MODE_DGRAD>(p, st, "lin_dgrad_mfma");
+  return launch_lin<T, MODE_DGRAD>(p, split, st, "lin_dgrad_mfma");
 }
 
 // dgrad + LayerNorm backward in one kernel; writes dX and a [*nslab][2][K] slab of d(gamma)/d(beta) partials
@@ -1415,7 +1415,7 @@ namespace {
 template <typename T>
 int wgrad_impl(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, const float* stats, int in_act,
                const T* dY, int64_t lddy, float* dW, float* dbias, float* slab, int64_t M, int K, int N, float s,
-               const float* Wt_fin, float* G, float* dln_w, float* dln_b, hipStream_t st) {
+               const float* Wt_fin, float* G, float* dln_w, float* dln_b, bool split, hipStream_t st) {
   const bool lnfin = G != nullptr;   // LayerNorm finish: x-hat slabs, then dW/dbias/d(gamma)/d(beta) from G
   if (mfma_disabled() || !rows_ok<T>(X, ldx) || !rows_ok<T>(dY, lddy)) return RDST_ENOTSUP;
   WgradArgs<T> p{};
@@ -1430,8 +1430,7 @@ int wgrad_impl(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, co
   // LDS row strides: bf16 rows are read by ds_read_b64_tr_b16 (4 token rows x 64 B per 32 lanes):
   // stride = 64 (mod 256) bytes puts the 4 rows on disjoint bank ranges; fp32 rows are read 32
   // consecutive floats at a time, any stride works.
-  bool split = false;
-  if constexpr (sizeof(T) == 4) split = rdst_split();
+  split = sizeof(T) == 4 && split;
   auto stride = [split](int elems) {   // (split mode: two bf16 planes in the bytes of the fp32 row, read like bf16 rows)
     const int b = elems * (int)sizeof(T);
     if (sizeof(T) == 4 && !split) return b;
@@ -1481,25 +1480,25 @@ int wgrad_impl(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, co
 template <typename T>
 int linear_wgrad_mfma(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, const float* stats, int in_act,
                       const T* dY, int64_t lddy, float* dW, float* dbias, float* slab, int64_t M, int K, int N, float s,
-                      hipStream_t st) {
+                      bool split, hipStream_t st) {
   return wgrad_impl<T>(X, ldx, ln_w, ln_b, stats, in_act, dY, lddy, dW, dbias, slab, M, K, N, s, nullptr, nullptr, nullptr,
-                       nullptr, st);
+                       nullptr, split, st);
 }
 
 // LayerNorm-fused Linear: dW, dbias AND d(gamma), d(beta) from one pass over (x-hat, dY).  G: N*(K+1) floats of scratch.
 template <typename T>
 int linear_wgrad_ln_mfma(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, const float* stats, const float* Wt,
                          const T* dY, int64_t lddy, float* dW, float* dbias, float* dln_w, float* dln_b, float* slab,
-                         float* G, int64_t M, int K, int N, float s, hipStream_t st) {
+                         float* G, int64_t M, int K, int N, float s, bool split, hipStream_t st) {
   if (!ln_w || !ln_b || !stats || !Wt || !G) return RDST_ENOTSUP;
-  return wgrad_impl<T>(X, ldx, ln_w, ln_b, stats, 0, dY, lddy, dW, dbias, slab, M, K, N, s, Wt, G, dln_w, dln_b, st);
+  return wgrad_impl<T>(X, ldx, ln_w, ln_b, stats, 0, dY, lddy, dW, dbias, slab, M, K, N, s, Wt, G, dln_w, dln_b, split, st);
 }
 
 // dgrad + LayerNorm backward, dX only (d(gamma)/d(beta) come from linear_wgrad_ln_mfma); K <= 128
 template <typename T>
 int linear_dgrad_ln2_mfma(const T* X, int64_t ldx, const float* stats, const float* gamma, const float* Wt, const T* dY,
                           int64_t lddy, T* dX, int64_t lddx, const T* acc, int64_t ldacc, int64_t M, int K, int N, float s,
-                          hipStream_t st) {
+                          bool split, hipStream_t st) {
   using MM = Mma<T>;
   if (mfma_disabled() || K > 128 || !dX) return RDST_ENOTSUP;
   const int64_t rowbytes = (int64_t)N * (int64_t)sizeof(T);
@@ -1521,7 +1520,7 @@ int linear_dgrad_ln2_mfma(const T* X, int64_t ldx, const float* stats, const flo
   {                                                                                                                  \
     auto kern = lin_dgrad_ln2_kernel<T, NC>;                                                                         \
     if constexpr (sizeof(T) == 4)                                                                                    \
-      if (rdst_split()) kern = lin_dgrad_ln2_kernel<T, NC, true>;                                                    \
+      if (split) kern = lin_dgrad_ln2_kernel<T, NC, true>;                                                           \
     if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, st, p);                                          \
   }
@@ -1535,15 +1534,15 @@ int linear_dgrad_ln2_mfma(const T* X, int64_t ldx, const float* stats, const flo
                                        T*, int64_t, const T*, int64_t, float*, int*, int64_t, int, int, float,         \
                                        hipStream_t);                                                                   \
   template int linear_fwd_mfma<T>(const T*, int64_t, const float*, const float*, int, const float*, const float*,     \
-                                  const T*, int64_t, T*, int64_t, float*, int64_t, int, int, float, hipStream_t);     \
+                                  const T*, int64_t, T*, int64_t, float*, int64_t, int, int, float, bool, hipStream_t); \
   template int linear_dgrad_mfma<T>(const T*, int64_t, bool, int, const float*, const T*, int64_t, T*, int64_t,       \
-                                    const T*, int64_t, float*, int64_t, int, int, float, hipStream_t);                \
+                                    const T*, int64_t, float*, int64_t, int, int, float, bool, hipStream_t);          \
   template int linear_wgrad_mfma<T>(const T*, int64_t, const float*, const float*, const float*, int, const T*,       \
-                                    int64_t, float*, float*, float*, int64_t, int, int, float, hipStream_t);         \
+                                    int64_t, float*, float*, float*, int64_t, int, int, float, bool, hipStream_t);   \
   template int linear_wgrad_ln_mfma<T>(const T*, int64_t, const float*, const float*, const float*, const float*,     \
                                        const T*, int64_t, float*, float*, float*, float*, float*, float*, int64_t,    \
-                                       int, int, float, hipStream_t);                                                 \
+                                       int, int, float, bool, hipStream_t);                                           \
   template int linear_dgrad_ln2_mfma<T>(const T*, int64_t, const float*, const float*, const float*, const T*, int64_t, \
-                                        T*, int64_t, const T*, int64_t, int64_t, int, int, float, hipStream_t);
+                                        T*, int64_t, const T*, int64_t, int64_t, int, int, float, bool, hipStream_t);
 INST(float)
 INST(bf16)

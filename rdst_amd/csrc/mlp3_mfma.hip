@@ -374,11 +374,13 @@ int launch_m3(M3Args& p, hipStream_t st) {
 
 size_t mlp3_pack_bytes(int C, int hid) { return lin3_pack_bytes(C, hid) + lin3_pack_bytes(hid, C); }
 
+bool mlp3_fwd_shape(int C, int hid) { return hid == 2 * C && (C == 60 || C == 90 || C == 120); }
+
 // packs: [fc1 image: lin3 layout for (N = hid, K = C, gamma / beta folded)][fc2 image: (N = C, K = hid)]
 int mlp3_fwd_bf16(const bf16* X, int64_t ldx, const float* ln_w, const float* ln_b, const float* W1, const float* b1, const float* W2,
                   const float* b2, bf16* Y, int64_t ldy, float* stats, int64_t M, int C, int hid, void* wpack, bool prepacked,
                   hipStream_t st) {
-  if (!wpack || ((uintptr_t)wpack & 15) || hid != 2 * C || !(C == 60 || C == 90 || C == 120) || M <= 0) return RDST_ENOTSUP;
+  if (!wpack || ((uintptr_t)wpack & 15) || !mlp3_fwd_shape(C, hid) || M <= 0) return RDST_ENOTSUP;
   if (((uintptr_t)X & 3) || (ldx & 1) || ((uintptr_t)Y & 3) || (ldy & 1)) return RDST_ENOTSUP;
   const int64_t xb = ((M - 1) * ldx + C) * 2;
   if (xb >= (1ll << 31) || M * ldy * 2 >= (1ll << 31)) return RDST_ENOTSUP;

@@ -1228,19 +1228,24 @@ int mlp_nct(int C, int hid) {
   return nct;
 }
 
+// the fused Mlp kernels (bf16 rows) cover (C, hid)
+bool mlp_fused(int C, int hid) {
+  static int off = -1;
+  if (off < 0) {
+    const char* e = rdst_dbg_getenv("RDST_MLP_V1");
+    off = (e && e[0] == '1') ? 1 : 0;
+  }
+  return !off && mlp_nct(C, hid) != 0;
+}
+
 }  // namespace
 
 int wgrad_ln_finish_launch(const float* G, const float* Wt, const float* ln_w, const float* ln_b, int N, int K, float s,
                            float* dW, float* dbias, float* dln_w, float* dln_b, hipStream_t st);
 
 extern "C" int rdst_mlp_fused_supported(int C, int hid, int dtype) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
-  static int off = -1;
-  if (off < 0) {
-    const char* e = rdst_dbg_getenv("RDST_MLP_V1");
-    off = (e && e[0] == '1') ? 1 : 0;
-  }
-  return (!off && dtype == RDST_BF16 && mlp_nct(C, hid) != 0) ? 1 : 0;
+  if (rdst_dtype(dtype, "rdst_mlp_fused_supported")) return 0;
+  return dtype == RDST_BF16 && mlp_fused(C, hid);
 }
 
 extern "C" size_t rdst_mlp_bwd_workspace(int64_t M, int C, int hid) {
@@ -1254,11 +1259,11 @@ extern "C" int rdst_mlp_bwd(const void* X, int64_t ld_x, const float* ln_w, cons
                             const float* W1, const float* b1, const float* W2, const void* dY, int64_t ld_dy, void* dX,
                             int64_t ld_dx, float* dW1, float* db1, float* dW2, float* db2, float* dln_w, float* dln_b,
                             void* workspace, size_t workspace_bytes, int64_t M, int C, int hid, int dtype, void* stream) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
+  if (int rc = rdst_dtype(dtype, "rdst_mlp_bwd")) return rc;
   if (!X || !ln_w || !ln_b || !stats || !W1 || !W2 || !dY || !dX || !dW1 || !db1 || !dW2 || !db2 || !dln_w || !dln_b || !workspace)
     return rdst_fail(RDST_EINVAL, "rdst_mlp_bwd: null pointer");
   if (M < 0 || C <= 0 || hid <= 0 || ld_x < C || ld_dy < C || ld_dx < C) return rdst_fail(RDST_EINVAL, "rdst_mlp_bwd: bad dimensions");
-  if (!rdst_mlp_fused_supported(C, hid, dtype)) return RDST_ENOTSUP;
+  if (dtype != RDST_BF16 || !mlp_fused(C, hid)) return RDST_ENOTSUP;
   if (((uintptr_t)X & 3) || ((uintptr_t)dY & 3) || ((uintptr_t)dX & 3) || (ld_x & 1) || (ld_dy & 1) || (ld_dx & 1)) return RDST_ENOTSUP;
   if (workspace_bytes < rdst_mlp_bwd_workspace(M, C, hid)) return rdst_fail(RDST_EINVAL, "rdst_mlp_bwd: workspace too small");
   if (M == 0) return 0;
@@ -1336,17 +1341,17 @@ extern "C" size_t rdst_mlp_fwd_workspace(int C, int hid) {
   return mlp3_pack_bytes(C, hid);
 }
 extern "C" int rdst_mlp_fwd_packable(int C, int hid, int dtype) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
-  return dtype == RDST_BF16 && hid == 2 * C && (C == 60 || C == 90 || C == 120);
+  if (rdst_dtype(dtype, "rdst_mlp_fwd_packable")) return 0;
+  return dtype == RDST_BF16 && mlp3_fwd_shape(C, hid);   // mlp3_mfma.hip
 }
 
 extern "C" int rdst_mlp_fwd(const void* X, int64_t ld_x, const float* ln_w, const float* ln_b, const float* W1, const float* b1,
                             const float* W2, const float* b2, void* Y, int64_t ld_y, float* stats, void* workspace,
                             size_t workspace_bytes, int64_t M, int C, int hid, int dtype, void* stream) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
+  if (int rc = rdst_dtype(dtype, "rdst_mlp_fwd")) return rc;
   if (!X || !ln_w || !ln_b || !W1 || !W2 || !Y || !stats) return rdst_fail(RDST_EINVAL, "rdst_mlp_fwd: null pointer");
   if (M < 0 || C <= 0 || hid <= 0 || ld_x < C || ld_y < C) return rdst_fail(RDST_EINVAL, "rdst_mlp_fwd: bad dimensions");
-  if (!rdst_mlp_fused_supported(C, hid, dtype)) return RDST_ENOTSUP;
+  if (dtype != RDST_BF16 || !mlp_fused(C, hid)) return RDST_ENOTSUP;
   if (((uintptr_t)X & 3) || ((uintptr_t)Y & 3) || (ld_x & 1) || (ld_y & 1) || hid < 8) return RDST_ENOTSUP;
   if (M == 0) return 0;
   hipStream_t st = (hipStream_t)stream;

@@ -518,7 +518,6 @@ __global__ void __launch_bounds__(256) dice_bwd_kernel(const T* __restrict__ lg,
 
 // ---- launch helpers --------------------------------------------------------------------------------------------------
 int vec_ok(const char* who, int C, int dtype) {
-  if (dtype != RDST_F32 && dtype != RDST_BF16) return rdst_fail(RDST_EINVAL, "%s: bad dtype %d", who, dtype);
   const int vn = dtype == RDST_F32 ? 4 : 8;
   if (C <= 0 || C % vn) return rdst_fail(RDST_ENOTSUP, "%s: C = %d must be a multiple of %d", who, C, vn);
   const int lpp = C / vn;
@@ -547,7 +546,7 @@ extern "C" size_t rdst_u_scratch_bytes(void) { return SCRATCH; }
 extern "C" int rdst_u_bn_stats(const void* X, int64_t ld, int64_t P, int C, const float* gamma, const float* beta, float eps,
                                float momentum, float* running_mean, float* running_var, float* coef, void* scratch, int dtype,
                                void* stream) {
-  if (dtype == RDST_F32X3) dtype = RDST_F32;
+  if (int rc = rdst_dtype(dtype, "rdst_u_bn_stats")) return rc;
   if (!X || !gamma || !beta || !coef || !scratch || P <= 0) return rdst_fail(RDST_EINVAL, "rdst_u_bn_stats: bad argument");
   if (int rc = vec_ok("rdst_u_bn_stats", C, dtype)) return rc;
   if (C > MAXC) return rdst_fail(RDST_ENOTSUP, "rdst_u_bn_stats: C = %d > %d", C, MAXC);
@@ -585,7 +584,7 @@ extern "C" int rdst_u_bn_stats_from(const float* partials, int nblk, int64_t P, 
 
 extern "C" int rdst_u_bn_apply(const void* X, int64_t ldx, const float* coef, const void* X2, int64_t ldx2, const float* coef2,
                                const void* R, int64_t ldr, int relu, void* Y, int64_t ldy, int64_t P, int C, int dtype, void* stream) {
-  if (dtype == RDST_F32X3) dtype = RDST_F32;
+  if (int rc = rdst_dtype(dtype, "rdst_u_bn_apply")) return rc;
   if (!X || !coef || !Y || P <= 0 || (X2 && !coef2)) return rdst_fail(RDST_EINVAL, "rdst_u_bn_apply: bad argument");
   if (int rc = vec_ok("rdst_u_bn_apply", C, dtype)) return rc;
   hipStream_t st = (hipStream_t)stream;
@@ -602,7 +601,7 @@ extern "C" int rdst_u_bn_apply(const void* X, int64_t ldx, const float* coef, co
 extern "C" int rdst_u_bn_bwd(const void* dY, int64_t lddy, const void* Ymask, int64_t ldm, const void* Xraw, int64_t ldx,
                              const float* coef, void* dX, int64_t lddx, void* Gout, int64_t ldg, const void* Gadd, int64_t ldga,
                              int64_t P, int C, void* scratch, int dtype, void* stream) {
-  if (dtype == RDST_F32X3) dtype = RDST_F32;
+  if (int rc = rdst_dtype(dtype, "rdst_u_bn_bwd")) return rc;
   if (!dY || !Xraw || !coef || !dX || !scratch || P <= 0) return rdst_fail(RDST_EINVAL, "rdst_u_bn_bwd: bad argument");
   if (int rc = vec_ok("rdst_u_bn_bwd", C, dtype)) return rc;
   if (C > MAXC) return rdst_fail(RDST_ENOTSUP, "rdst_u_bn_bwd: C = %d > %d", C, MAXC);
@@ -629,7 +628,7 @@ extern "C" int rdst_u_bn_bwd(const void* dY, int64_t lddy, const void* Ymask, in
 
 extern "C" int rdst_u_maxpool_fwd(const void* X, int64_t ldx, void* Y, int64_t ldy, uint8_t* idx, int B, int H, int W, int C, int dtype,
                                   void* stream) {
-  if (dtype == RDST_F32X3) dtype = RDST_F32;
+  if (int rc = rdst_dtype(dtype, "rdst_u_maxpool_fwd")) return rc;
   if (!X || !Y || !idx || B <= 0 || H <= 0 || W <= 0) return rdst_fail(RDST_EINVAL, "rdst_u_maxpool_fwd: bad argument");
   if (int rc = vec_ok("rdst_u_maxpool_fwd", C, dtype)) return rc;
   const int64_t P = (int64_t)B * ((H + 1) / 2) * ((W + 1) / 2);
@@ -643,7 +642,7 @@ extern "C" int rdst_u_maxpool_fwd(const void* X, int64_t ldx, void* Y, int64_t l
 
 extern "C" int rdst_u_maxpool_bwd(const void* dY, int64_t lddy, const uint8_t* idx, const void* add, int64_t ld_add, void* dX,
                                   int64_t lddx, int B, int H, int W, int C, int dtype, void* stream) {
-  if (dtype == RDST_F32X3) dtype = RDST_F32;
+  if (int rc = rdst_dtype(dtype, "rdst_u_maxpool_bwd")) return rc;
   if (!dY || !dX || !idx || B <= 0 || H <= 0 || W <= 0) return rdst_fail(RDST_EINVAL, "rdst_u_maxpool_bwd: bad argument");
   if (int rc = vec_ok("rdst_u_maxpool_bwd", C, dtype)) return rc;
   const int64_t P = (int64_t)B * H * W;
@@ -659,7 +658,7 @@ extern "C" int rdst_u_maxpool_bwd(const void* dY, int64_t lddy, const uint8_t* i
 
 extern "C" int rdst_u_sumpool2(const void* dY, int64_t lddy, const void* add, int64_t ld_add, void* dX, int64_t lddx, int B, int H, int W,
                                int C, int dtype, void* stream) {
-  if (dtype == RDST_F32X3) dtype = RDST_F32;
+  if (int rc = rdst_dtype(dtype, "rdst_u_sumpool2")) return rc;
   if (!dY || !dX || B <= 0 || H <= 0 || W <= 0) return rdst_fail(RDST_EINVAL, "rdst_u_sumpool2: bad argument");
   if (int rc = vec_ok("rdst_u_sumpool2", C, dtype)) return rc;
   const int64_t P = (int64_t)B * H * W;
@@ -674,9 +673,8 @@ extern "C" int rdst_u_sumpool2(const void* dY, int64_t lddy, const void* add, in
 }
 
 extern "C" int rdst_u_stem_fwd(const float* img, const float* W, void* Y, int64_t ld_y, int B, int Cin, int H, int Wd, int dtype, void* stream) {
-  if (dtype == RDST_F32X3) dtype = RDST_F32;
+  if (int rc = rdst_dtype(dtype, "rdst_u_stem_fwd")) return rc;
   if (!img || !W || !Y || B <= 0 || H <= 0 || Wd <= 0 || Cin <= 0 || Cin > 4 || ld_y < SC) return rdst_fail(RDST_EINVAL, "rdst_u_stem_fwd: bad argument");
-  if (dtype != RDST_F32 && dtype != RDST_BF16) return rdst_fail(RDST_EINVAL, "rdst_u_stem_fwd: bad dtype");
   Geo g{B, H, Wd, (H + 1) / 2, (Wd + 1) / 2, Cin};
   const unsigned grid = stemconv::fwd_grid(g);
   if (dtype == RDST_F32) hipLaunchKernelGGL((stemconv::fwd_kernel<float>), dim3(grid), dim3(256), 0, (hipStream_t)stream, img, W, (float*)Y, ld_y, g);
@@ -686,9 +684,8 @@ extern "C" int rdst_u_stem_fwd(const float* img, const float* W, void* Y, int64_
 
 extern "C" int rdst_u_stem_dgrad(const void* dR, int64_t ld, const float* W, const float* upstream, float* dimg, int B, int Cin, int H,
                                  int Wd, int dtype, void* stream) {
-  if (dtype == RDST_F32X3) dtype = RDST_F32;
+  if (int rc = rdst_dtype(dtype, "rdst_u_stem_dgrad")) return rc;
   if (!dR || !W || !dimg || B <= 0 || H <= 0 || Wd <= 0 || Cin <= 0 || Cin > 4 || ld < SC) return rdst_fail(RDST_EINVAL, "rdst_u_stem_dgrad: bad argument");
-  if (dtype != RDST_F32 && dtype != RDST_BF16) return rdst_fail(RDST_EINVAL, "rdst_u_stem_dgrad: bad dtype");
   Geo g{B, H, Wd, (H + 1) / 2, (Wd + 1) / 2, Cin};
   const unsigned grid = stemconv::dgrad_grid(g);
   if (dtype == RDST_F32) hipLaunchKernelGGL((stemconv::dgrad_kernel<float>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)dR, ld, W, upstream, dimg, g);
@@ -698,7 +695,7 @@ extern "C" int rdst_u_stem_dgrad(const void* dR, int64_t ld, const float* W, con
 
 extern "C" int rdst_u_pair_loss_fwd(const void* A, int64_t lda, const void* Bv, int64_t ldb, int64_t P, int C, int mse, float weight,
                                     int accumulate, float* loss, void* scratch, int dtype, void* stream) {
-  if (dtype == RDST_F32X3) dtype = RDST_F32;
+  if (int rc = rdst_dtype(dtype, "rdst_u_pair_loss_fwd")) return rc;
   if (!A || !Bv || !loss || !scratch || P <= 0) return rdst_fail(RDST_EINVAL, "rdst_u_pair_loss_fwd: bad argument");
   if (int rc = vec_ok("rdst_u_pair_loss_fwd", C, dtype)) return rc;
   hipStream_t st = (hipStream_t)stream;
@@ -713,7 +710,7 @@ extern "C" int rdst_u_pair_loss_fwd(const void* A, int64_t lda, const void* Bv, 
 extern "C" int rdst_u_pair_loss_bwd(const void* A, int64_t lda, const void* Bv, int64_t ldb, int64_t P, int C, int mse, float weight,
                                     const float* upstream, const void* add, int64_t ld_add, void* dA, int64_t ldda, int dtype,
                                     void* stream) {
-  if (dtype == RDST_F32X3) dtype = RDST_F32;
+  if (int rc = rdst_dtype(dtype, "rdst_u_pair_loss_bwd")) return rc;
   if (!A || !Bv || !dA || P <= 0) return rdst_fail(RDST_EINVAL, "rdst_u_pair_loss_bwd: bad argument");
   if (int rc = vec_ok("rdst_u_pair_loss_bwd", C, dtype)) return rc;
   const float scale = (float)((double)weight / ((double)P * C));
@@ -730,10 +727,9 @@ extern "C" int rdst_u_pair_loss_bwd(const void* A, int64_t lda, const void* Bv, 
 extern "C" int rdst_u_dice_fwd(const void* logits, int64_t ld, const void* target_logits, int64_t ldt, const int64_t* labels, int64_t P,
                                int ncls, int class_mask, float eps, float weight, int accumulate, float* loss, float* coef, void* scratch,
                                int dtype, void* stream) {
-  if (dtype == RDST_F32X3) dtype = RDST_F32;
+  if (int rc = rdst_dtype(dtype, "rdst_u_dice_fwd")) return rc;
   if (!logits || (!target_logits && !labels) || !loss || !coef || !scratch || P <= 0) return rdst_fail(RDST_EINVAL, "rdst_u_dice_fwd: bad argument");
   if (ncls <= 0 || ncls > MAXCLS) return rdst_fail(RDST_ENOTSUP, "rdst_u_dice_fwd: ncls = %d (1..%d)", ncls, MAXCLS);
-  if (dtype != RDST_F32 && dtype != RDST_BF16) return rdst_fail(RDST_EINVAL, "rdst_u_dice_fwd: bad dtype");
   hipStream_t st = (hipStream_t)stream;
   float* part = (float*)((char*)scratch + OFF_PART);
   int64_t nb = P / 1024;
@@ -749,10 +745,9 @@ extern "C" int rdst_u_dice_fwd(const void* logits, int64_t ld, const void* targe
 extern "C" int rdst_u_dice_bwd(const void* logits, int64_t ld, const void* target_logits, int64_t ldt, const int64_t* labels, int64_t P,
                                int ncls, const float* coef, const float* upstream, void* dlogits, int64_t ldd, int ncls_pad, int dtype,
                                void* stream) {
-  if (dtype == RDST_F32X3) dtype = RDST_F32;
+  if (int rc = rdst_dtype(dtype, "rdst_u_dice_bwd")) return rc;
   if (!logits || (!target_logits && !labels) || !coef || !dlogits || P <= 0) return rdst_fail(RDST_EINVAL, "rdst_u_dice_bwd: bad argument");
   if (ncls <= 0 || ncls > MAXCLS || ncls_pad < ncls || ldd < ncls_pad) return rdst_fail(RDST_EINVAL, "rdst_u_dice_bwd: bad class counts");
-  if (dtype != RDST_F32 && dtype != RDST_BF16) return rdst_fail(RDST_EINVAL, "rdst_u_dice_bwd: bad dtype");
   int64_t g = (P + 255) / 256;
   g = g > 8192 ? 8192 : g;
   if (dtype == RDST_F32)

@@ -685,12 +685,13 @@ extern "C" int rdst_u_conv(const void* X1, int64_t ld1, int C1, int up1, const v
                            const float* bias, const void* add, int64_t ld_add, void* Y, int64_t ld_y, int B, int Hin, int Win,
                            int Hout, int Wout, int Cout, int Npad, int ksize, int stride, int transposed, int dtype, void* stream,
                            const float* bn1, float* stats, int* stats_blocks) {
+  bool split;
+  if (int rc = rdst_dtype(dtype, split, "rdst_u_conv")) return rc;
   if (!X1 || !Wp || !Y) return rdst_fail(RDST_EINVAL, "rdst_u_conv: null pointer");
   if (stats && (!stats_blocks || bias || add || ksize != 3 || stride != 1))
     return rdst_fail(RDST_ENOTSUP, "rdst_u_conv: stats needs the 3x3 stride-1 form without bias / addend (and stats_blocks)");
   if (bn1 && (dtype == RDST_BF16 || ksize != 3 || stride != 1 || transposed || (C1 * 4) % 64 || ((C1 + C2) * 4) % 64 || ((uintptr_t)bn1 & 3)))
     return rdst_fail(RDST_ENOTSUP, "rdst_u_conv: bn1 (BatchNorm + ReLU on the way in) needs the fp32 / fp32x3 3x3 stride-1 forward form");
-  if (dtype != RDST_F32 && dtype != RDST_BF16 && dtype != RDST_F32X3) return rdst_fail(RDST_EINVAL, "rdst_u_conv: bad dtype %d", dtype);
   if (B <= 0 || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0 || C1 <= 0 || C2 < 0 || Cout <= 0)
     return rdst_fail(RDST_EINVAL, "rdst_u_conv: bad shape");
   if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2)) return rdst_fail(RDST_ENOTSUP, "rdst_u_conv: k = %d stride = %d", ksize, stride);
@@ -716,6 +717,6 @@ extern "C" int rdst_u_conv(const void* X1, int64_t ld1, int C1, int up1, const v
     const char* e = rdst_dbg_getenv("RDST_UCONV_DBG");
     p.dbg = e ? atoi(e) : 0;
   }
-  if (dtype == RDST_F32X3) return pick_kb<float, true>(p, (hipStream_t)stream);
+  if (split) return pick_kb<float, true>(p, (hipStream_t)stream);
   return dtype == RDST_F32 ? pick_kb<float, false>(p, (hipStream_t)stream) : pick_kb<bf16, false>(p, (hipStream_t)stream);
 }

@@ -63,11 +63,10 @@ int launch(bool fwd, const void* src, int64_t lds, void* dst, int64_t ldd, int B
   return rdst_launch_status(fwd ? "rdst_upsample2_fwd" : "rdst_upsample2_bwd");
 }
 
-int check(const char* who, const void* a, const void* b, int64_t lda, int64_t ldb, int B, int H, int W, int C, int dtype) {
+int check(const char* who, const void* a, const void* b, int64_t lda, int64_t ldb, int B, int H, int W, int C) {
   if (!a || !b) return rdst_fail(RDST_EINVAL, "%s: null pointer", who);
   if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return rdst_fail(RDST_EINVAL, "%s: bad shape B=%d H=%d W=%d C=%d", who, B, H, W, C);
   if (lda < C || ldb < C) return rdst_fail(RDST_EINVAL, "%s: leading dimension smaller than C=%d", who, C);
-  if (dtype != RDST_F32 && dtype != RDST_BF16) return rdst_fail(RDST_EINVAL, "%s: bad dtype %d", who, dtype);
   return 0;
 }
 
@@ -75,16 +74,16 @@ int check(const char* who, const void* a, const void* b, int64_t lda, int64_t ld
 
 extern "C" int rdst_upsample2_fwd(const void* x, int64_t ld_x, void* y, int64_t ld_y, int B, int H, int W, int C, int dtype,
                                   void* stream) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
-  if (int rc = check("rdst_upsample2_fwd", x, y, ld_x, ld_y, B, H, W, C, dtype)) return rc;
+  if (int rc = rdst_dtype(dtype, "rdst_upsample2_fwd")) return rc;
+  if (int rc = check("rdst_upsample2_fwd", x, y, ld_x, ld_y, B, H, W, C)) return rc;
   return dtype == RDST_F32 ? launch<float>(true, x, ld_x, y, ld_y, B, H, W, C, (hipStream_t)stream)
                            : launch<bf16>(true, x, ld_x, y, ld_y, B, H, W, C, (hipStream_t)stream);
 }
 
 extern "C" int rdst_upsample2_bwd(const void* dy, int64_t ld_dy, void* dx, int64_t ld_dx, int B, int H, int W, int C, int dtype,
                                   void* stream) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
-  if (int rc = check("rdst_upsample2_bwd", dy, dx, ld_dy, ld_dx, B, H, W, C, dtype)) return rc;
+  if (int rc = rdst_dtype(dtype, "rdst_upsample2_bwd")) return rc;
+  if (int rc = check("rdst_upsample2_bwd", dy, dx, ld_dy, ld_dx, B, H, W, C)) return rc;
   return dtype == RDST_F32 ? launch<float>(false, dy, ld_dy, dx, ld_dx, B, H, W, C, (hipStream_t)stream)
                            : launch<bf16>(false, dy, ld_dy, dx, ld_dx, B, H, W, C, (hipStream_t)stream);
 }

@@ -66,9 +66,10 @@ int wattn_fwd_generic(const void* qkv, int64_t ld, const float* table, void* out
 int wattn_bwd_generic(const void* qkv, int64_t ld, const float* table, const void* dout, int64_t ldd, void* dqkv,
                       int64_t ldq, float* slab, const WinGeom& g, float scale, int dtype, hipStream_t st);
 
-// gfx950 matrix-core kernels (wattn_mfma.hip): RDST_ENOTSUP when the shape is not covered
+// gfx950 matrix-core kernels (wattn_mfma.hip): RDST_ENOTSUP when the shape is not covered; split (fp32 rows only): the
+// RDST_F32X3 form of the kernels (common.h)
 int wattn_fwd_mfma(const void* qkv, int64_t ld, const float* table, void* out, int64_t ldo, const WinGeom& g,
-                   float scale, int dtype, hipStream_t st);
+                   float scale, int dtype, bool split, hipStream_t st);
 // K1 specialised for bf16, ws 8, 6 heads of dim 10/15/20 (wattn_mfma_hd.hip); RDST_ENOTSUP otherwise
 int wattn_fwd_mfma_hd(const void* qkv, int64_t ld, const float* table, void* out, int64_t ldo, const WinGeom& g,
                       float scale, hipStream_t st);
@@ -90,7 +91,7 @@ int wattn_bwd_pair(const void* qkv, int64_t ld, const float* table, const void* 
 int wattn_bwd_mfma_hd(const void* qkv, int64_t ld, const float* table, const void* dout, int64_t ldd, void* dqkv,
                       int64_t ldq, float* slab, int slab_rows, const WinGeom& g, float scale, int* nslab, hipStream_t st);
 int wattn_bwd_mfma(const void* qkv, int64_t ld, const float* table, const void* dout, int64_t ldd, void* dqkv,
-                   int64_t ldq, float* slab, int slab_rows, const WinGeom& g, float scale, int dtype, int* nslab,
+                   int64_t ldq, float* slab, int slab_rows, const WinGeom& g, float scale, int dtype, bool split, int* nslab,
                    hipStream_t st);
 
 // K8 (swinattn_fwd.hip): LayerNorm + qkv -> window attention -> proj + shortcut in one launch (bf16, ws 8, 6 heads, C = 60 / 90 / 120)

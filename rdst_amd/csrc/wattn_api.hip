@@ -4,7 +4,6 @@
 #include "reduce_batch.h"
 
 thread_local char g_rdst_err[256] = {0};
-thread_local int g_rdst_split = 0;
 
 extern "C" int rdst_abi_version(void) { return 11; }
 extern "C" const char* rdst_last_error(void) { return g_rdst_err; }
@@ -32,13 +31,13 @@ int make_geom(WinGeom& g, int B, int H, int W, int C, int heads, int ws, int shi
 extern "C" int rdst_wattn_fwd(const void* qkv, int64_t ld_qkv, const float* table, const float* mask, int mask_nw,
                               void* out, int64_t ld_out, int B, int H, int W, int C, int heads, int ws, int shift,
                               float scale, int dtype, void* stream) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
+  bool split;
+  if (int rc = rdst_dtype(dtype, split, "rdst_wattn_fwd")) return rc;
   WinGeom g;
   if (int rc = make_geom(g, B, H, W, C, heads, ws, shift, mask, mask_nw, "rdst_wattn_fwd")) return rc;
   if (!qkv || !table || !out) return rdst_fail(RDST_EINVAL, "rdst_wattn_fwd: null pointer");
-  if (dtype != RDST_F32 && dtype != RDST_BF16) return rdst_fail(RDST_EINVAL, "rdst_wattn_fwd: bad dtype %d", dtype);
   if (ld_qkv < 3 * C || ld_out < C) return rdst_fail(RDST_EINVAL, "rdst_wattn_fwd: leading dimension too small");
-  if (int rc = wattn_fwd_mfma(qkv, ld_qkv, table, out, ld_out, g, scale, dtype, (hipStream_t)stream); rc != RDST_ENOTSUP)
+  if (int rc = wattn_fwd_mfma(qkv, ld_qkv, table, out, ld_out, g, scale, dtype, split, (hipStream_t)stream); rc != RDST_ENOTSUP)
     return rc;
   return wattn_fwd_generic(qkv, ld_qkv, table, out, ld_out, g, scale, dtype, (hipStream_t)stream);
 }
@@ -55,12 +54,12 @@ extern "C" int rdst_wattn_bwd(const void* qkv, int64_t ld_qkv, const float* tabl
                               const void* dout, int64_t ld_dout, void* dqkv, int64_t ld_dqkv, float* dtable,
                               void* workspace, size_t workspace_bytes, int B, int H, int W, int C, int heads, int ws,
                               int shift, float scale, int dtype, void* stream) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
+  bool split;
+  if (int rc = rdst_dtype(dtype, split, "rdst_wattn_bwd")) return rc;
   WinGeom g;
   if (int rc = make_geom(g, B, H, W, C, heads, ws, shift, mask, mask_nw, "rdst_wattn_bwd")) return rc;
   if (!qkv || !table || !dout || !dqkv || !dtable || !workspace)
     return rdst_fail(RDST_EINVAL, "rdst_wattn_bwd: null pointer");
-  if (dtype != RDST_F32 && dtype != RDST_BF16) return rdst_fail(RDST_EINVAL, "rdst_wattn_bwd: bad dtype %d", dtype);
   if (ld_qkv < 3 * C || ld_dqkv < 3 * C || ld_dout < C)
     return rdst_fail(RDST_EINVAL, "rdst_wattn_bwd: leading dimension too small");
   if (workspace_bytes < rdst_wattn_bwd_workspace(B, H, W, C, heads, ws))
@@ -69,7 +68,7 @@ extern "C" int rdst_wattn_bwd(const void* qkv, int64_t ld_qkv, const float* tabl
   float* slab = (float*)workspace;
   int nwin = B * g.nWh * g.nWw;
   int nslab = 0;
-  int rc = wattn_bwd_mfma(qkv, ld_qkv, table, dout, ld_dout, dqkv, ld_dqkv, slab, nwin, g, scale, dtype, &nslab, st);
+  int rc = wattn_bwd_mfma(qkv, ld_qkv, table, dout, ld_dout, dqkv, ld_dqkv, slab, nwin, g, scale, dtype, split, &nslab, st);
   if (rc == 0) {
     nwin = nslab;  // one slab row per persistent workgroup
   } else {
@@ -84,8 +83,8 @@ extern "C" int rdst_wattn_bwd(const void* qkv, int64_t ld_qkv, const float* tabl
 
 // ---- K8: the attention half of a Swin block in one launch (swinattn_fwd.hip) ---------------------------------------------------
 extern "C" int rdst_swin_attn_fwd_supported(int C, int heads, int ws, int dtype) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
-  return (dtype == RDST_BF16 && swinattn_supported(C, heads, ws)) ? 1 : 0;
+  if (rdst_dtype(dtype, "rdst_swin_attn_fwd_supported")) return 0;
+  return dtype == RDST_BF16 && swinattn_supported(C, heads, ws);
 }
 extern "C" size_t rdst_swin_attn_fwd_workspace(int C) { return C > 0 ? swinattn_pack_bytes(C) : 0; }
 extern "C" int rdst_swin_attn_fwd(const void* X, int64_t ld_x, const float* ln_w, const float* ln_b, const float* Wqkv,
@@ -93,12 +92,11 @@ extern "C" int rdst_swin_attn_fwd(const void* X, int64_t ld_x, const float* ln_w
                                   int64_t ld_qkv, void* a, int64_t ld_a, void* x1, int64_t ld_x1, float* stats, void* workspace,
                                   size_t workspace_bytes, int B, int H, int W, int C, int heads, int ws, int shift, float scale,
                                   int dtype, void* stream) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
+  if (int rc = rdst_dtype(dtype, "rdst_swin_attn_fwd")) return rc;
   WinGeom g;
   if (int rc = make_geom(g, B, H, W, C, heads, ws, shift, nullptr, 0, "rdst_swin_attn_fwd")) return rc;
   if (!X || !ln_w || !ln_b || !Wqkv || !table || !Wproj || !qkv || !a || !x1 || !stats || !workspace)
     return rdst_fail(RDST_EINVAL, "rdst_swin_attn_fwd: null pointer");
-  if (dtype != RDST_F32 && dtype != RDST_BF16) return rdst_fail(RDST_EINVAL, "rdst_swin_attn_fwd: bad dtype %d", dtype);
   if (ld_x < C || ld_qkv < 3 * C || ld_a < C || ld_x1 < C) return rdst_fail(RDST_EINVAL, "rdst_swin_attn_fwd: leading dimension too small");
   if (dtype != RDST_BF16) return RDST_ENOTSUP;
   const bool prepacked = workspace_bytes == RDST_PREPACKED;
@@ -113,7 +111,7 @@ extern "C" int rdst_swin_attn_fwd(const void* X, int64_t ld_x, const float* ln_w
 // serve with other kernels: the caller then uses rdst_wattn_fwd / rdst_wattn_bwd.
 extern "C" int rdst_wattn_fwd_lse(const void* qkv, int64_t ld_qkv, const float* table, void* out, int64_t ld_out, float* nlse,
                                   int B, int H, int W, int C, int heads, int ws, int shift, float scale, int dtype, void* stream) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
+  if (int rc = rdst_dtype(dtype, "rdst_wattn_fwd_lse")) return rc;
   WinGeom g;
   if (int rc = make_geom(g, B, H, W, C, heads, ws, shift, nullptr, 0, "rdst_wattn_fwd_lse")) return rc;
   if (!qkv || !table || !out || !nlse) return rdst_fail(RDST_EINVAL, "rdst_wattn_fwd_lse: null pointer");
@@ -126,7 +124,7 @@ extern "C" int rdst_wattn_bwd_lse(const void* qkv, int64_t ld_qkv, const float* 
                                   const void* out, int64_t ld_out, const float* nlse, void* dqkv, int64_t ld_dqkv, float* dtable,
                                   void* workspace, size_t workspace_bytes, int B, int H, int W, int C, int heads, int ws,
                                   int shift, float scale, int dtype, void* stream) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
+  if (int rc = rdst_dtype(dtype, "rdst_wattn_bwd_lse")) return rc;
   WinGeom g;
   if (int rc = make_geom(g, B, H, W, C, heads, ws, shift, nullptr, 0, "rdst_wattn_bwd_lse")) return rc;
   if (!qkv || !table || !dout || !out || !nlse || !dqkv || !dtable || !workspace)
@@ -164,11 +162,10 @@ int drop_args(WinGeom& g, float attn_drop, const unsigned long long* seed, const
 extern "C" int rdst_wattn_fwd_drop(const void* qkv, int64_t ld_qkv, const float* table, const float* mask, int mask_nw,
                                    void* out, int64_t ld_out, int B, int H, int W, int C, int heads, int ws, int shift,
                                    float scale, int dtype, float attn_drop, const unsigned long long* seed, void* stream) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
+  if (int rc = rdst_dtype(dtype, "rdst_wattn_fwd_drop")) return rc;
   WinGeom g;
   if (int rc = make_geom(g, B, H, W, C, heads, ws, shift, mask, mask_nw, "rdst_wattn_fwd_drop")) return rc;
   if (!qkv || !table || !out) return rdst_fail(RDST_EINVAL, "rdst_wattn_fwd_drop: null pointer");
-  if (dtype != RDST_F32 && dtype != RDST_BF16) return rdst_fail(RDST_EINVAL, "rdst_wattn_fwd_drop: bad dtype %d", dtype);
   if (ld_qkv < 3 * C || ld_out < C) return rdst_fail(RDST_EINVAL, "rdst_wattn_fwd_drop: leading dimension too small");
   if (int rc = drop_args(g, attn_drop, seed, "rdst_wattn_fwd_drop")) return rc;
   return wattn_fwd_generic(qkv, ld_qkv, table, out, ld_out, g, scale, dtype, (hipStream_t)stream);
@@ -179,12 +176,11 @@ extern "C" int rdst_wattn_bwd_drop(const void* qkv, int64_t ld_qkv, const float*
                                    void* workspace, size_t workspace_bytes, int B, int H, int W, int C, int heads, int ws,
                                    int shift, float scale, int dtype, float attn_drop, const unsigned long long* seed,
                                    void* stream) {
-  SplitScope split_scope(dtype);   // RDST_F32X3: fp32 rows, split-bf16 GEMMs where a kernel has the form (common.h)
+  if (int rc = rdst_dtype(dtype, "rdst_wattn_bwd_drop")) return rc;
   WinGeom g;
   if (int rc = make_geom(g, B, H, W, C, heads, ws, shift, mask, mask_nw, "rdst_wattn_bwd_drop")) return rc;
   if (!qkv || !table || !dout || !dqkv || !dtable || !workspace)
     return rdst_fail(RDST_EINVAL, "rdst_wattn_bwd_drop: null pointer");
-  if (dtype != RDST_F32 && dtype != RDST_BF16) return rdst_fail(RDST_EINVAL, "rdst_wattn_bwd_drop: bad dtype %d", dtype);
   if (ld_qkv < 3 * C || ld_dqkv < 3 * C || ld_dout < C)
     return rdst_fail(RDST_EINVAL, "rdst_wattn_bwd_drop: leading dimension too small");
   if (workspace_bytes < rdst_wattn_bwd_workspace(B, H, W, C, heads, ws))

@@ -541,7 +541,7 @@ bool mfma_disabled() {
 
 template <typename T>
 int launch_bwd(const T* qkv, int64_t ld, const float* table, const T* dout, int64_t ldd, T* dqkv, int64_t ldq,
-               float* slab, int slab_rows, const WinGeom& g, float scale, int* nslab, hipStream_t st) {
+               float* slab, int slab_rows, const WinGeom& g, float scale, int* nslab, bool split, hipStream_t st) {
   const int d = g.C / g.heads;
   if (g.ws != 8 || g.heads != HEADS || d > 32 || g.C > 128 || g.mask) return RDST_ENOTSUP;
   WbArgs<T> p{};
@@ -571,7 +571,7 @@ int launch_bwd(const T* qkv, int64_t ld, const float* table, const T* dout, int6
   {                                                                                                                  \
     auto kern = wattn_bwd_mfma_kernel<T, GR, IT, NWV, CT>;                                                                 \
     if constexpr (sizeof(T) == 4)                                                                                    \
-      if (rdst_split()) kern = wattn_bwd_mfma_kernel<T, GR, IT, NWV, CT, true>;                                      \
+      if (split) kern = wattn_bwd_mfma_kernel<T, GR, IT, NWV, CT, true>;                                             \
     if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * NWV), smem, st, p);                                        \
   }
@@ -598,7 +598,7 @@ int launch_bwd(const T* qkv, int64_t ld, const float* table, const T* dout, int6
 
 // slab: [>= 256][heads][225] floats; *nslab = number of slab rows written (to be reduced by the caller)
 int wattn_bwd_mfma(const void* qkv, int64_t ld, const float* table, const void* dout, int64_t ldd, void* dqkv,
-                   int64_t ldq, float* slab, int slab_rows, const WinGeom& g, float scale, int dtype, int* nslab,
+                   int64_t ldq, float* slab, int slab_rows, const WinGeom& g, float scale, int dtype, bool split, int* nslab,
                    hipStream_t st) {
   if (mfma_disabled()) return RDST_ENOTSUP;
   if (dtype == RDST_F32) {
@@ -606,7 +606,7 @@ int wattn_bwd_mfma(const void* qkv, int64_t ld, const float* table, const void* 
                                    scale, nslab, st);   // 16x16 windows
     if (rc != RDST_ENOTSUP) return rc;
     return launch_bwd<float>((const float*)qkv, ld, table, (const float*)dout, ldd, (float*)dqkv, ldq, slab, slab_rows, g,
-                             scale, nslab, st);
+                             scale, nslab, split, st);
   }
 #ifndef RDST_K2_DMA
 #define RDST_K2_DMA 6   // bit mask over the head dims 10 / 15 / 20 (1 / 2 / 4): which widths take the round-4 re-cut (wattn_bwd_pair.hip:
@@ -633,5 +633,5 @@ int wattn_bwd_mfma(const void* qkv, int64_t ld, const float* table, const void* 
     if (rc != RDST_ENOTSUP) return rc;
   }
   return launch_bwd<bf16>((const bf16*)qkv, ld, table, (const bf16*)dout, ldd, (bf16*)dqkv, ldq, slab, slab_rows, g, scale,
-                          nslab, st);
+                          nslab, false, st);
 }

@@ -371,7 +371,7 @@ int pick_gran(uintptr_t a, uintptr_t b, int64_t lda_bytes, int64_t ldb_bytes, in
 
 template <typename T>
 int launch_fwd(const T* qkv, int64_t ld, const float* table, T* out, int64_t ldo, const WinGeom& g, float scale,
-               hipStream_t st) {
+               bool split, hipStream_t st) {
   const int d = g.C / g.heads;
   if (g.ws != 8 || d > 32 || g.C > 128 || g.mask) return RDST_ENOTSUP;
   WaArgs<T> p{};
@@ -398,7 +398,7 @@ int launch_fwd(const T* qkv, int64_t ld, const float* table, T* out, int64_t ldo
   {                                                                                                                  \
     auto kern = wattn_fwd_mfma_kernel<T, GR, KM, NWV>;                                                               \
     if constexpr (sizeof(T) == 4)                                                                                    \
-      if (rdst_split()) kern = wattn_fwd_mfma_kernel<T, GR, KM, NWV, true>;                                          \
+      if (split) kern = wattn_fwd_mfma_kernel<T, GR, KM, NWV, true>;                                                 \
     if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * NWV), smem, st, p);                                     \
   }
@@ -420,12 +420,12 @@ int launch_fwd(const T* qkv, int64_t ld, const float* table, T* out, int64_t ldo
 }  // namespace
 
 int wattn_fwd_mfma(const void* qkv, int64_t ld, const float* table, void* out, int64_t ldo, const WinGeom& g,
-                   float scale, int dtype, hipStream_t st) {
+                   float scale, int dtype, bool split, hipStream_t st) {
   if (mfma_disabled()) return RDST_ENOTSUP;
   if (dtype == RDST_F32) {
     const int rc = wattn16_fwd_f32((const float*)qkv, ld, table, (float*)out, ldo, g, scale, st);   // 16x16 windows
     if (rc != RDST_ENOTSUP) return rc;
-    return launch_fwd<float>((const float*)qkv, ld, table, (float*)out, ldo, g, scale, st);
+    return launch_fwd<float>((const float*)qkv, ld, table, (float*)out, ldo, g, scale, split, st);
   }
   {  // the compile-time-specialised kernel (6 heads of dim 10/15/20) where it applies
     const int rc = wattn_fwd_mfma_hd(qkv, ld, table, out, ldo, g, scale, st);
@@ -435,5 +435,5 @@ int wattn_fwd_mfma(const void* qkv, int64_t ld, const float* table, void* out, i
     const int rc = wattn16_fwd_mfma(qkv, ld, table, out, ldo, g, scale, st);
     if (rc != RDST_ENOTSUP) return rc;
   }
-  return launch_fwd<bf16>((const bf16*)qkv, ld, table, (bf16*)out, ldo, g, scale, st);
+  return launch_fwd<bf16>((const bf16*)qkv, ld, table, (bf16*)out, ldo, g, scale, false, st);
 }
