@@ -415,6 +415,23 @@ int rdst_u_dice_bwd(const void* logits, int64_t ld, const void* target_logits, i
                     int ncls, const float* coef, const float* upstream, void* dlogits, int64_t ldd, int ncls_pad, int dtype,
                     void* stream);
 
+/* ---- PSNR / SSIM scores of super-resolved images (rdst_amd/metrics.py on the device) ------------------------------------
+ * Replaces the host-side scikit-image calls of metrics/sr_metrics.py:8-14 (peak_signal_noise_ratio and
+ * structural_similarity(data_range, multichannel=True)) after the border crop of metrics/sr_metrics.py:108-115, for a batch
+ * of N images of one shape.  gt, pred: fp32 NCHW, contiguous.  Each image is cropped by `margin` pixels on every side
+ * first; then, per image and in fp64 (every fp32 value is converted once, exactly):
+ *   mse[n]  = mean over all channels of the cropped image of (gt - pred)^2  (PSNR = 10 log10(data_range^2 / mse), inf at 0);
+ *   ssim[n] = mean over the channels of the mean SSIM map over the cropped image without (win-1)/2 pixels at each edge:
+ *             win x win uniform window, sample covariance (NP / (NP - 1), NP = win^2), C1 = (0.01 data_range)^2,
+ *             C2 = (0.03 data_range)^2 (scikit-image's defaults).  The windows of that interior lie inside the crop, so
+ *             the filter's reflected border never enters the result and no pixel outside the crop is read.
+ * win odd in [3, 15]; both cropped sides >= win; data_range > 0; N * C * H * W <= 2^31.  `workspace` = device memory of
+ * at least rdst_sr_scores_workspace(...) bytes (0 for bad arguments): one fp64 pair per workgroup, summed per image in a
+ * fixed order by a second kernel — the results are bit-identical run to run (no atomics). */
+size_t rdst_sr_scores_workspace(int N, int C, int H, int W, int margin, int win);
+int rdst_sr_scores(const float* gt, const float* pred, int N, int C, int H, int W, int margin, int win, double data_range,
+                   double* mse, double* ssim, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

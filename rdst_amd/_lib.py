@@ -81,6 +81,9 @@ SIGNATURES = {
     "rdst_u_pair_loss_bwd": (_i, [_p, _l, _p, _l, _l, _i, _i, _f, _p, _p, _l, _p, _l, _i, _p]),
     "rdst_u_dice_fwd": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _f, _f, _i, _p, _p, _p, _i, _p]),
     "rdst_u_dice_bwd": (_i, [_p, _l, _p, _l, _p, _l, _i, _p, _p, _p, _l, _i, _i, _p]),
+    # PSNR / SSIM scoring (rdst_amd.metrics.device_scores)
+    "rdst_sr_scores_workspace": (_z, [_i, _i, _i, _i, _i, _i]),
+    "rdst_sr_scores": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, C.c_double, _p, _p, _p, _z, _p]),
 }
 
 ABI_VERSION = 11             # must equal rdst_abi_version() of the loaded library (argument lists change between versions)

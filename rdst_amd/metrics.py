@@ -11,6 +11,9 @@ scikit-image is not installed in the build image, so this is a restatement of th
     borders), K1 = 0.01, K2 = 0.03, sample covariance (N / (N - 1)), mean over the map cropped by (win - 1) / 2 pixels,
     averaged over channels.  **Parity unpinned** (no scikit-image here to generate vectors from); the tests check the
     definition on closed-form cases.
+
+``device_scores`` computes both on the GPU (the HIP kernel behind rdst_sr_scores, include/rdst_hip.h) to this file's float64
+precision, with only 2 N doubles per batch left for the host; ``SRMetrics(..., device="cuda")`` scores tensors with it.
 """
 from __future__ import annotations
 
@@ -90,12 +93,73 @@ def _to_hwc_list(imgs, margin: int) -> List[np.ndarray]:
     return [a] if a.ndim == 3 else list(a)
 
 
+def device_scores(gt, pred, margin: int = 0, data_range: float = 1.0, win_size: int = 7):
+    """Per-image ``(mse, ssim)`` of fp32 CUDA tensors (N, C, H, W) or (C, H, W) after cropping ``margin`` border pixels, as
+    float64 CUDA tensors of length N: ``psnr`` and ``ssim`` above (``psnr = 10 log10(data_range^2 / mse)``), computed on the
+    device in float64 by one HIP kernel and a fixed-order sum (bit-identical run to run), enqueued on the current stream
+    without a host sync (graph-capturable)."""
+    import torch
+    from . import _lib
+    if not (isinstance(gt, torch.Tensor) and isinstance(pred, torch.Tensor)):
+        raise TypeError("device_scores: gt and pred must be torch tensors")
+    if gt.dtype != torch.float32 or pred.dtype != torch.float32:
+        raise TypeError(f"device_scores: gt and pred must be float32 tensors, got {gt.dtype} and {pred.dtype}")
+    if gt.dim() == 3:
+        gt, pred = gt.unsqueeze(0), pred.unsqueeze(0)
+    if gt.dim() != 4:
+        raise AssertionError("images should have 3 or 4 dimensions")
+    margin, win_size = int(margin), int(win_size)
+    if margin < 0:
+        raise ValueError(f"device_scores: margin={margin} must not be negative")
+    if win_size % 2 == 0 or not 3 <= win_size <= 15:
+        raise ValueError(f"device_scores: win_size={win_size} must be odd and in [3, 15]")
+    if not data_range > 0:
+        raise ValueError(f"device_scores: data_range={data_range} must be positive")
+    N, C, H, W = gt.shape
+    if gt.shape != pred.shape or min(H, W) - 2 * margin < win_size:
+        raise ValueError("ssim: images must have the same shape and be at least win_size in both dimensions")
+    if not (gt.is_cuda and pred.is_cuda) or gt.device != pred.device:
+        raise ValueError("device_scores: gt and pred must be CUDA tensors on one device")
+    gt, pred = gt.detach().contiguous(), pred.detach().contiguous()
+    lib = _lib.load()
+    ws_bytes = lib.rdst_sr_scores_workspace(N, C, H, W, margin, win_size)
+    if ws_bytes == 0:
+        _lib.check(_lib.EINVAL, "rdst_sr_scores_workspace")
+    with torch.cuda.device(gt.device):
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=gt.device)
+        out = torch.empty(2, N, dtype=torch.float64, device=gt.device)
+        _lib.check(lib.rdst_sr_scores(gt.data_ptr(), pred.data_ptr(), N, C, H, W, margin, win_size, float(data_range),
+                                      out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(), ws_bytes,
+                                      torch.cuda.current_stream().cuda_stream), "rdst_sr_scores")
+    return out[0], out[1]
+
+
+def psnr_from_mse(mse: float, data_range: float = 1.0) -> float:
+    """``psnr`` above from its mean squared error."""
+    if mse == 0:
+        return float("inf")
+    return float(10.0 * math.log10((data_range ** 2) / mse))
+
+
+def _as_batch(imgs):
+    """A (N, C, H, W) / (C, H, W) tensor or a list of (C, H, W) tensors -> one fp32 (N, C, H, W) tensor."""
+    import torch
+    if isinstance(imgs, (list, tuple)) and len(imgs) and all(isinstance(t, torch.Tensor) for t in imgs):
+        imgs = torch.stack([t.detach() for t in imgs])
+    if not isinstance(imgs, torch.Tensor):
+        raise TypeError("SRMetrics(device=...): images must be torch tensors or lists of tensors")
+    return imgs.detach().float()
+
+
 class SRMetrics:
     """The pixel metrics of the reference's ``SRMetrics`` that the shipped configs ask for ('psnr ssim',
     config_files/RDST_E1_OASIS_example_SRx4.ini): ``SRMetrics('psnr ssim')(gts, preds, margin)`` -> {'psnr': [...], ...}.
-    The other metrics of the reference (sewar's, FID) are outside this repository's scope and raise."""
+    The other metrics of the reference (sewar's, FID) are outside this repository's scope and raise.
+    ``device="cuda"``: tensors (a batch or a list of images) are scored on the GPU by ``device_scores`` (the ground truth
+    and the predictions are moved there if they are not on it), with one host copy of the 2 N results per call; anything
+    else raises TypeError.  ``device=None`` (default): the host path above."""
 
-    def __init__(self, metrics: str = "psnr ssim", return_mode: str = "full"):
+    def __init__(self, metrics: str = "psnr ssim", return_mode: str = "full", device=None):
         self.metrics = metrics.split()
         for m in self.metrics:
             if m not in _FUNCS:
@@ -103,10 +167,30 @@ class SRMetrics:
         if return_mode not in ("full", "mean"):
             raise ValueError("return mode must be one of [mean, full]")
         self.return_mode = return_mode
+        self.device = None
+        if device is not None:
+            import torch
+            self.device = torch.device(device)
+            if self.device.type != "cuda":
+                raise ValueError(f"SRMetrics: device must be None or a CUDA device, got {device!r}")
+
+    def _device_report(self, gts, preds, margin: int) -> Dict[str, List[float]]:
+        import torch
+        g, p = _as_batch(gts), _as_batch(preds)
+        dev = p.device if p.is_cuda else g.device if g.is_cuda else self.device
+        mse, ss = device_scores(g.to(dev), p.to(dev), margin)
+        host = torch.stack((mse, ss)).cpu().tolist()
+        rep = {}
+        for m in self.metrics:
+            rep[m] = [psnr_from_mse(v) for v in host[0]] if m == "psnr" else host[1]
+        return rep
 
     def __call__(self, gts, preds, margin: int = 0) -> Dict[str, Union[List[float], float]]:
-        g, p = _to_hwc_list(gts, margin), _to_hwc_list(preds, margin)
-        rep = {m: [_FUNCS[m](a, b) for a, b in zip(g, p)] for m in self.metrics}
+        if self.device is not None:
+            rep = self._device_report(gts, preds, margin)
+        else:
+            g, p = _to_hwc_list(gts, margin), _to_hwc_list(preds, margin)
+            rep = {m: [_FUNCS[m](a, b) for a, b in zip(g, p)] for m in self.metrics}
         if self.return_mode == "mean":
             rep = {m: float(np.mean(v)) for m, v in rep.items()}
         return rep

@@ -272,6 +272,28 @@ _PLANS: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()   # owner modu
 
 def pack_plan_of(owner) -> Optional[PackPlan]:
     return _PLANS.get(owner)
+
+
+class keep_pack_plan:
+    """``with ops.keep_pack_plan(module):`` around forwards of another kind than the usual ones (an inference pass between
+    training steps): they may use, drop or record the module's plan; on exit the plan the module had before, or its absence,
+    is put back, so the packed arena that a captured HIP graph reads stays alive and in use."""
+
+    def __init__(self, owner):
+        self.owner = owner
+
+    def __enter__(self):
+        self.plan = _PLANS.get(self.owner)
+        return self
+
+    def __exit__(self, *exc):
+        if self.plan is None:
+            _PLANS.pop(self.owner, None)
+        else:
+            _PLANS[self.owner] = self.plan
+        return False
+
+
 PACK_LINEAR, PACK_CONV3_FWD, PACK_LINEAR_SEC3, PACK_LINEAR_X3, PACK_CONV3_FWD_X3 = 0, 1, 2, 3, 4
 
 

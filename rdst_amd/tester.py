@@ -22,6 +22,7 @@ class SRTester:
         self.batch_size = int(batch_size)
         self.sr_scale = float(sr_scale if sr_scale is not None else getattr(net, "sr_scale", getattr(net, "upscale", 1)))
         self.metrics = SRMetrics(metrics, "full")
+        self.device_metrics = SRMetrics(metrics, "full", device="cuda")
         if compute_dtype is not None and hasattr(net, "set_compute_dtype"):
             net.set_compute_dtype(compute_dtype)
 
@@ -33,7 +34,11 @@ class SRTester:
         rec = [self.net(p.to(dev)) for p in lr_img.split(self.batch_size * 4)]
         return torch.cat(rec, dim=0)
 
-    def evaluate(self, lr_img: torch.Tensor, gt_img: torch.Tensor) -> Dict[str, List[float]]:
-        """Scores of metrics/sr_evaluation.py:152: per-image metrics after cropping ceil(sr_scale) border pixels."""
+    def evaluate(self, lr_img: torch.Tensor, gt_img: torch.Tensor, on_device: bool = False) -> Dict[str, List[float]]:
+        """Scores of metrics/sr_evaluation.py:152: per-image metrics after cropping ceil(sr_scale) border pixels.
+        ``on_device=True``: the reconstruction stays on the GPU, ``gt_img`` is moved there once and both are scored there
+        (metrics.device_scores); only the per-image scores come back to the host."""
         rec = self.inference(lr_img)
+        if on_device:
+            return self.device_metrics(gt_img.to(rec.device), rec, int(math.ceil(self.sr_scale)))
         return self.metrics(gt_img, rec, int(math.ceil(self.sr_scale)))

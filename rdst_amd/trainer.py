@@ -16,6 +16,7 @@ reference ``checkpoint.tar`` resumes here and vice versa (FlatAdam keeps torch.o
 """
 from __future__ import annotations
 
+import math
 import time
 from typing import Callable, Dict, Optional, Sequence
 
@@ -212,6 +213,36 @@ class DPTrainStep:
         self._finish_step()
         self.training_epoch_costs.append(time.time() - t0)   # :176-178 (host-side enqueue time: nothing synced)
         return loss
+
+    def quick_eva(self, lr: torch.Tensor, hr: torch.Tensor, sr_scale: Optional[float] = None, metrics: str = "psnr ssim",
+                  num_samples: int = 64, batch_size: int = 16, generator: Optional[torch.Generator] = None,
+                  return_mode: str = "mean") -> dict:
+        """The quick validation of models/basic_trainer.py:257-286 (run every ``check_every`` iterations,
+        trans_sr_trainer.py:180-181) on validation slices the caller loaded: ``num_samples`` random slices of ``lr`` (N, C, h, w)
+        / ``hr`` (N, C, h*s, w*s) (torch.randperm with ``generator``; the reference shuffles with numpy) are super-resolved as
+        SRTester.inference does (eval mode, no_grad, chunks of batch_size * 4, the network's own compute mode) and scored on the
+        GPU (metrics.device_scores) after cropping ceil(s) border pixels.  The report, keyed as MetaSREvaluation keys it
+        (``psnr_4.0``, metrics/sr_evaluation.py:142-156), is appended to ``quick_validation_reports`` and returned.
+        The optimizer, the gradient bucket, the loss records, the packed weights and a captured graph are left as they were:
+        the next step() computes what it would have computed without this call."""
+        from . import ops
+        from .metrics import SRMetrics
+        scorer = SRMetrics(metrics, return_mode, device="cuda")
+        s = float(sr_scale if sr_scale is not None else getattr(self.net, "sr_scale", getattr(self.net, "upscale", 1)))
+        idx = torch.randperm(len(lr), generator=generator)[:int(num_samples)]
+        dev = next(self.net.parameters()).device
+        modes = [(m, m.training) for m in self.net.modules()]
+        self.net.eval()
+        try:
+            with torch.no_grad(), ops.keep_pack_plan(self.net):
+                rec = torch.cat([self.net(p.to(dev)) for p in lr[idx.to(lr.device)].split(int(batch_size) * 4)])
+        finally:
+            for m, t in modes:
+                m.training = t
+        rep = scorer(hr[idx.to(hr.device)].to(dev), rec, int(math.ceil(s)))
+        report = {f"{m}_{s}": v for m, v in rep.items()}
+        self.quick_validation_reports.append(report)
+        return report
 
     def _finish_step(self) -> None:
         self.bucket.all_reduce_mean(self.group)        # no-op on one rank
