@@ -432,6 +432,31 @@ size_t rdst_sr_scores_workspace(int N, int C, int H, int W, int margin, int win)
 int rdst_sr_scores(const float* gt, const float* pred, int N, int C, int H, int W, int margin, int win, double data_range,
                    double* mse, double* ssim, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Training batches cut and degraded on the device (rdst_amd/data.py) ---------------------------------------------------
+ * The bicubic resize of datasets/basic_dataset.py:65-123 (cv2.resize(INTER_CUBIC) on float images; equally
+ * torch.nn.functional.interpolate(mode="bicubic", align_corners=False, antialias=False)): separable, four taps per axis,
+ * Keys kernel with a = -0.75, source coordinate (dst + 0.5) * in / out - 0.5, tap indices clamped to the image, no
+ * antialiasing, values not clamped.  A tap table of an axis is device memory, 16-byte aligned: `out` rows of four int32
+ * source indices and `out` rows of four fp32 weights, taps in ascending order, computed by the host in float64 and rounded
+ * once (rdst_amd.data.tap_table).  The kernels clamp every index they read into the image.  Every output is the vertical
+ * 4-tap sum of four horizontal 4-tap sums, taps ascending, one fmaf per tap, in both entry points: the same pixels give the
+ * same bits.
+ *
+ * Resize: x fp32 (N, C, H, W) -> y fp32 (N, C, oh, ow), contiguous, any positive sizes, down or up. */
+int rdst_resize_bicubic(const float* x, float* y, int N, int C, int H, int W, int oh, int ow, const int32_t* tap_index_y,
+                        const float* tap_weight_y, const int32_t* tap_index_x, const float* tap_weight_x, void* stream);
+/* Sampler: the batch of BasicMultiSRTrain.__getitem__ (datasets/basic_dataset.py:190-217 with the crop of :482-499) in ONE
+ * launch, from a resident stack of slices fp32 (S, C, H, W) and `index`, DEVICE memory of B x 3 int32 (slice, top, left)
+ * that the host never reads: every origin is clamped into the stack by the kernel.  Writes hr (B, C, hp, hp) = the
+ * windows, lr (B, C, lp, lp) = the resize of each window, and, with `labels` uint8 (S, H, W) and `label_out` (B, hp, hp)
+ * (both or neither), the label windows.  hp == 4 * lp with a 16-byte aligned hr (and 4-byte aligned label_out) takes the
+ * fast path (the taps of an LR pixel are its own 4 x 4 HR pixels, weights -3/32, 19/32, 19/32, -3/32) and needs no table;
+ * everything else takes the table of the (hp -> lp) axis.  RDST_EINVAL if hp exceeds H or W; RDST_ENOTSUP if hp is wider
+ * than the table path's LDS tile holds (about 3000). */
+int rdst_sample_patches(const float* stack, const uint8_t* labels, const int32_t* index, float* hr, float* lr,
+                        uint8_t* label_out, int S, int C, int H, int W, int B, int hp, int lp, const int32_t* tap_index,
+                        const float* tap_weight, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -84,6 +84,9 @@ SIGNATURES = {
     # PSNR / SSIM scoring (rdst_amd.metrics.device_scores)
     "rdst_sr_scores_workspace": (_z, [_i, _i, _i, _i, _i, _i]),
     "rdst_sr_scores": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, C.c_double, _p, _p, _p, _z, _p]),
+    # bicubic degradation and the training-batch sampler (rdst_amd.data)
+    "rdst_resize_bicubic": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "rdst_sample_patches": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
 }
 
 ABI_VERSION = 11             # must equal rdst_abi_version() of the loaded library (argument lists change between versions)

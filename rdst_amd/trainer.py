@@ -57,6 +57,7 @@ class DPTrainStep:
         self.loss_module = loss_fn if hasattr(loss_fn, "state_dict") else torch.nn.Module()
         self.loss_threshold = float(loss_threshold)
         self.last_report = None        # the (lazy) per-component report of the last step, SRLoss-shaped losses only
+        self.last_batch = None         # the batch of the last step_from()
         # graph capture
         self.use_graph = bool(graph)
         self.graph_warmup = int(graph_warmup)
@@ -213,6 +214,22 @@ class DPTrainStep:
         self._finish_step()
         self.training_epoch_costs.append(time.time() - t0)   # :176-178 (host-side enqueue time: nothing synced)
         return loss
+
+    def step_from(self, sampler) -> torch.Tensor:
+        """``step()`` on a fresh batch of a ``rdst_amd.data.DevicePatchSampler`` (``last_batch`` keeps it).  Once a graph is
+        captured and the batch has its shapes, the sampler writes straight into the tensors the graph reads, so ``step()``
+        finds them in place and copies nothing; the sampler's launch is on the stream of the replay, so the previous replay
+        has finished reading them.  Labels stay in the batch for the caller's own loop: ``step()`` takes none."""
+        draw = sampler.draw()
+        out = None
+        if self.graph is not None and self.loss_threshold >= GUARD_OFF and self._static is not None:
+            lr_shape, hr_shape = sampler.batch_shapes(draw)
+            if (tuple(self._static[0].shape) == lr_shape and tuple(self._static[1].shape) == hr_shape
+                    and self._static[0].dtype == torch.float32 and self._static[1].dtype == torch.float32
+                    and self._static[0].device == sampler.device):
+                out = self._static
+        self.last_batch = sampler.sample(out=out, draw=draw)
+        return self.step(self.last_batch["in"], self.last_batch["out"])
 
     def quick_eva(self, lr: torch.Tensor, hr: torch.Tensor, sr_scale: Optional[float] = None, metrics: str = "psnr ssim",
                   num_samples: int = 64, batch_size: int = 16, generator: Optional[torch.Generator] = None,
