@@ -457,6 +457,26 @@ int rdst_sample_patches(const float* stack, const uint8_t* labels, const int32_t
                         uint8_t* label_out, int S, int C, int H, int W, int B, int hp, int lp, const int32_t* tap_index,
                         const float* tap_weight, void* stream);
 
+/* ---- Tiled whole-slice inference (rdst_amd/tiling.py) ----------------------------------------------------------------------
+ * The reference's ImageFolder / UnFolder / Folder (datasets/basic_dataset.py:347-449: nn.Unfold, the network on the patches,
+ * nn.Fold and a multiply by the reciprocal of the cover count) as two copy kernels.  A tile plan of an axis of n pixels is
+ * (patch, stride, pad, L): tile t covers the padded coordinates [t * stride, t * stride + patch), the image sits at
+ * [pad, pad + n).  Both entry points refuse (RDST_EINVAL) a plan that leaves a pixel uncovered: stride > patch,
+ * L <= 0 or (L - 1) * stride + patch < pad + n on an axis.  Tiles are numbered slice-major, then tile row, then tile column
+ * (the order of nn.Unfold(...).transpose(1, 2)).
+ *
+ * Unfold: x fp32 (N, C, H, W) -> out fp32 (n_slots, C, p, p), contiguous: slot k holds tile first_tile + k of the
+ * N * Ly * Lx tiles; slots past the last tile are zeros.  pad_mode 0: pixels outside the image are zeros (nn.Unfold's
+ * padding); 1: the edge is repeated (the source index is clamped).  A pure copy. */
+int rdst_unfold_tiles(const float* x, float* out, int N, int C, int H, int W, int p, int s, int pad_y, int pad_x, int Ly,
+                      int Lx, int pad_mode, int64_t first_tile, int n_slots, void* stream);
+/* Fold: tiles fp32 (N * Ly * Lx, C, P, P) -> out fp32 (N, C, H, W).  Every output pixel is gathered by one thread: the sum
+ * of the tile pixels that cover it, in fp32, in ascending tile row and then ascending tile column, times 1.0f / (float)count
+ * (one rounded reciprocal, one rounded multiply; the reference's fold(x) * (1. / divisor) with the divisor never stored).
+ * No atomics: the same bits on every run. */
+int rdst_fold_tiles(const float* tiles, float* out, int N, int C, int H, int W, int P, int S, int pad_y, int pad_x, int Ly,
+                    int Lx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

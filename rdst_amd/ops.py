@@ -274,6 +274,12 @@ def pack_plan_of(owner) -> Optional[PackPlan]:
     return _PLANS.get(owner)
 
 
+def install_pack_plan(owner, plan: PackPlan) -> None:
+    """Make ``plan`` (one that ``pack_plan_of(owner)`` returned earlier) the plan of the owner's next forwards; for use inside
+    ``keep_pack_plan(owner)``, which puts the previous one back."""
+    _PLANS[owner] = plan
+
+
 class keep_pack_plan:
     """``with ops.keep_pack_plan(module):`` around forwards of another kind than the usual ones (an inference pass between
     training steps): they may use, drop or record the module's plan; on exit the plan the module had before, or its absence,
