@@ -477,6 +477,72 @@ int rdst_unfold_tiles(const float* x, float* out, int N, int C, int H, int W, in
 int rdst_fold_tiles(const float* tiles, float* out, int N, int C, int H, int W, int P, int S, int pad_y, int pad_x, int Ly,
                     int Lx, void* stream);
 
+/* ---- Device-side step guard (rdst_amd/optim.py FlatAdam(device_state=True), rdst_amd/trainer.py device_guard) ------------
+ * The update guard of the reference's inner loop, models/trans_sr_trainer.py:162-174
+ *     if loss.item() < self.loss_threshold:  record; zero_grad; backward; optimizer.step(); scheduler.step()
+ * without the loss.item(): the decision, the step count (Adam's t, the scheduler's last_epoch) and the learning-rate
+ * schedule (utils/optim.py:56-75, MultiStepLR) live in device memory, so a guarded step never reads anything back and
+ * is graph-capturable.  The same pass also gives a skip on a non-finite gradient and global-norm clipping
+ * (torch.nn.utils.clip_grad_norm_), which the reference does not have.
+ *
+ * Step state: 48 bytes of 16-byte aligned device memory, written by ONE thread of rdst_step_guard with ordinary stores
+ * (last_lr alone is written by one thread of rdst_adam_step_dev; no thread of that launch reads it):
+ *   offset  0  int64   kept         updates applied so far = Adam's t = MultiStepLR's last_epoch
+ *   offset  8  int64   skipped      steps refused so far
+ *   offset 16  int32   last_keep    the latest decision: 1 = update, 0 = skip
+ *   offset 20  int32   last_reason  why it was a skip: RDST_SKIP_LOSS | RDST_SKIP_NONFINITE | RDST_SKIP_PEER (0 when kept)
+ *   offset 24  float   last_clip    the latest clip coefficient (1 when clipping is off or the norm is below max_grad_norm)
+ *   offset 28  float   last_lr      the learning rate of the latest APPLIED update
+ *   offset 32  double  last_sumsq   sum of squares of the latest gradient in fp64; -1 when it was not measured
+ *   offset 40  int64   reserved
+ * The host initialises it (kept = the step count to resume from, everything else 0) with a plain copy. */
+typedef struct rdst_step_state {
+  int64_t kept, skipped;
+  int32_t last_keep, last_reason;
+  float last_clip, last_lr;
+  double last_sumsq;
+  int64_t reserved;
+} rdst_step_state;
+#define RDST_SKIP_LOSS 1       /* !(loss < threshold): the reference's `if`, so a NaN loss skips */
+#define RDST_SKIP_NONFINITE 2  /* check_finite and the gradient's sum of squares is Inf or NaN */
+#define RDST_SKIP_PEER 4       /* *peer_skip != 0: some rank of the group asked to skip */
+
+/* The decision of one step:  keep = (loss < threshold) && *peer_skip == 0 && (!check_finite || isfinite(sumsq));
+ * kept += keep; skipped += !keep;  last_clip = min(1, max_grad_norm / (sqrt(sumsq) + 1e-6)) (clip_grad_norm_'s rule).
+ *   loss      : device fp32 scalar, compared as a double (what loss.item() < threshold compares); NULL = no loss test
+ *   peer_skip : device int32, or NULL (one rank).  Several ranks: MAX over the ranks of !(loss < threshold)
+ *   grad, n   : the flat fp32 gradient, 16-byte aligned.  It is read only when max_grad_norm > 0 or check_finite:
+ *               ONE pass with 16-byte loads, every element squared and accumulated in fp64 from the first add, one partial
+ *               per block in `workspace`, summed in a fixed order by the deciding block (no floating-point atomics: the
+ *               same bits on every run; an Inf or NaN element makes the sum non-finite, which is the finite test).
+ *               Otherwise the bucket is not touched, workspace may be NULL / 0 and the call is one 1-block launch.
+ *   max_grad_norm <= 0 : no clipping.
+ *   workspace : >= rdst_step_guard_workspace(n) bytes, 16-byte aligned. */
+size_t rdst_step_guard_workspace(int64_t n);
+int rdst_step_guard(const float* loss, double threshold, const int32_t* peer_skip, const float* grad, int64_t n,
+                    double max_grad_norm, int check_finite, void* workspace, size_t workspace_bytes, rdst_step_state* state,
+                    void* stream);
+
+/* MultiStepLR (utils/optim.py:56-75) as a table passed BY VALUE: lr[k] is the rate once k milestones have passed;
+ * milestones ascending (repeats allowed, as MultiStepLR counts them), count <= 16. */
+typedef struct rdst_lr_schedule {
+  int64_t milestones[16];
+  float lr[17];
+  int32_t count;
+} rdst_lr_schedule;
+
+/* rdst_adam_step (optimizer.step() + scheduler.step(), models/trans_sr_trainer.py:172-173) driven by the step state:
+ * t = state->kept (bias corrections 1 - beta^t in double on the device, as rdst_adam_step computes them on the host),
+ * lr = sched.lr[#{milestones <= t - 1}], and every gradient element is multiplied by state->last_clip AS IT IS READ:
+ * the gradient buffer itself is NOT rewritten (clip_grad_norm_ scales p.grad in place; here p.grad keeps the raw values).
+ * When state->last_keep == 0 the launch returns without touching param, exp_avg or exp_avg_sq.  Call it after
+ * rdst_step_guard on the same stream.  With last_clip == 1 a kept step writes the bits rdst_adam_step writes for the same
+ * step count and rate (the same expressions per element; pow on the device against the host's).  Same streaming shape as rdst_adam_step; its arguments do not change from step to
+ * step, so a captured launch replays as it is. */
+int rdst_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                       rdst_lr_schedule sched, float beta1, float beta2, float eps, float weight_decay,
+                       rdst_step_state* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

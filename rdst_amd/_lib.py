@@ -16,6 +16,15 @@ ACT_NONE, ACT_GELU, ACT_LEAKY02, ACT_LEAKY001 = 0, 1, 2, 3
 
 _p, _i, _l, _f, _z = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 
+
+class LrSchedule(C.Structure):   # rdst_lr_schedule, passed by value to rdst_adam_step_dev
+    MAX_MILESTONES = 16
+    _fields_ = [("milestones", C.c_int64 * 16), ("lr", C.c_float * 17), ("count", C.c_int32)]
+
+
+STEP_STATE_BYTES = 48            # rdst_step_state
+SKIP_LOSS, SKIP_NONFINITE, SKIP_PEER = 1, 2, 4
+
 # name -> (restype, argtypes); must list every symbol include/rdst_hip.h declares
 SIGNATURES = {
     "rdst_abi_version": (_i, []),
@@ -90,6 +99,10 @@ SIGNATURES = {
     # tiled whole-slice inference (rdst_amd.tiling)
     "rdst_unfold_tiles": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _l, _i, _p]),
     "rdst_fold_tiles": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    # the device-side step guard (rdst_amd.optim.FlatAdam(device_state=True))
+    "rdst_step_guard_workspace": (_z, [_l]),
+    "rdst_step_guard": (_i, [_p, C.c_double, _p, _p, _l, C.c_double, _i, _p, _z, _p, _p]),
+    "rdst_adam_step_dev": (_i, [_p, _p, _p, _p, _l, LrSchedule, _f, _f, _f, _f, _p, _p]),
 }
 
 ABI_VERSION = 11             # must equal rdst_abi_version() of the loaded library (argument lists change between versions)

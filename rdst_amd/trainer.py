@@ -9,7 +9,12 @@ What changes against the reference loop is only what data parallelism and the fl
     hyper-parameters (utils/optim.py:30-53) and scheduler (utils/optim.py:56-75);
   * the loss-threshold guard (trans_sr_trainer.py:162, ``loss.item() < loss_threshold``) costs a host
     sync per step; it is evaluated only when the threshold is below ``GUARD_OFF`` (the shipped ini sets
-    1e8, i.e. "never skip"), otherwise the step never leaves the device.
+    1e8, i.e. "never skip"), otherwise the step never leaves the device;
+  * ``device_guard=True`` makes the same decision in device memory (rdst_step_guard, include/rdst_hip.h): the step count,
+    the MultiStepLR rate and the keep / skip flag live there, so a guarded step reads nothing back and, on one rank, the
+    whole step (forward, loss, backward, guard, Adam) is ONE graph replay.  The order then is the fast path's — forward,
+    loss, backward, collectives, guard, Adam — so on several ranks the bucket all-reduce ALWAYS runs and its result is
+    discarded on a skipped step (the host cannot branch on a flag it never reads; the host guard skips the collective).
 ``save_checkpoint`` / ``load_checkpoint`` use the key layout of models/basic_trainer.py:164-208
 (``model_g``, ``optimizer_g``, ``scheduler_g``, ``loss`` state dicts + the training-state fields), so a
 reference ``checkpoint.tar`` resumes here and vice versa (FlatAdam keeps torch.optim.Adam's state layout).
@@ -36,22 +41,40 @@ class DPTrainStep:
     ``graph=True``: after ``graph_warmup`` eager steps on one input shape, forward + loss + backward are captured into ONE
     HIP graph and every later step of that shape replays it (the collective and the optimizer stay outside, so RCCL
     keeps its own streams); other shapes, and steps under an active loss-threshold guard, run eagerly.  This is the
-    step ``bench.py`` times."""
+    step ``bench.py`` times.
+    ``device_guard=True``: the loss-threshold guard (every threshold, GUARD_OFF included: a NaN loss always skips), a skip on
+    a non-finite averaged gradient (``skip_nonfinite``) and global-norm clipping (``max_grad_norm``, clip_grad_norm_'s
+    rule) are decided on the device; ``step()`` never takes the eager guarded branch and, on one rank, the captured graph
+    holds guard and Adam too.  ``guard_stats()`` / ``checkpoint()`` are the only reads of the step state."""
 
     RECORD_FLUSH = 4096   # parked device scalars before they are converted in one batch (bounds the memory they hold)
 
     def __init__(self, net: torch.nn.Module, lr: float = 1e-4, betas=(0.9, 0.99), eps: float = 1e-8,
                  weight_decay: float = 0.0, milestones: Optional[Sequence[int]] = None, gamma: float = 0.5,
                  loss_threshold: float = GUARD_OFF, loss_fn: Optional[Callable] = None, group=None,
-                 graph: bool = False, graph_warmup: int = 2):
+                 graph: bool = False, graph_warmup: int = 2, device_guard: bool = False,
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
+        self.device_guard = bool(device_guard)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        if self.device_guard and not all(p.is_cuda for p in net.parameters()):
+            raise ValueError("DPTrainStep(device_guard=True): the guard is a HIP kernel, the network must be on a GPU")
+        if not self.device_guard and (self.max_grad_norm is not None or self.skip_nonfinite):
+            raise ValueError("DPTrainStep: max_grad_norm and skip_nonfinite need device_guard=True")
         self.net = net
         self.group = group
         dp.broadcast_parameters(net, group=group)
         self.bucket = dp.FlatGradBucket(net.parameters())
         self.optimizer = FlatAdam(self.bucket.params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                  bucket=self.bucket)
+                                  bucket=self.bucket, device_state=self.device_guard)
         self.scheduler = (torch.optim.lr_scheduler.MultiStepLR(self.optimizer, milestones=list(milestones), gamma=gamma)
                           if milestones else None)
+        if self.device_guard and self.scheduler is not None:
+            # the object stays for the checkpoint layout; the rate comes from the device table, it is never stepped per step
+            self.optimizer.set_schedule(list(milestones), gamma)
+            self.optimizer.attach_scheduler(self.scheduler)
+        self._peer_skip = None         # device int32: MAX over the ranks of "my loss is not below the threshold"
+        self._graph_has_update = False  # the captured graph ends with guard + Adam (device_guard on one rank)
         self.loss_fn = loss_fn if loss_fn is not None else F.l1_loss      # SRLoss 'L1' (loss/sr_loss.py)
         # what the reference saves under 'loss' (basic_trainer.py:195): the loss object's own state_dict()
         self.loss_module = loss_fn if hasattr(loss_fn, "state_dict") else torch.nn.Module()
@@ -71,6 +94,7 @@ class DPTrainStep:
         self.training_loss_names = ["L1"] if loss_fn is None else list(getattr(loss_fn, "loss_components", ["loss"]))
         self.training_loss_records: Dict[str, list] = {n: [] for n in self.training_loss_names}
         self._pending: Dict[str, list] = {}      # device scalars of the steps since the last flush (see _record)
+        self._pending_keep: Dict[str, list] = {}  # device_guard: the decision of each parked step, next to its loss
         self.quick_validation_reports: list = []
         self.current_training_state_id = 0
         self.current_epoch = 0
@@ -97,25 +121,45 @@ class DPTrainStep:
         Here the DEVICE scalars of the step are parked (a clone each: the graph step overwrites its buffers) and become
         floats only when a checkpoint is written (`_flush_records`), so a step never leaves the device."""
         rep = self.last_report
+        # device_guard: the step's decision (rdst_step_state.last_keep) is parked next to the loss; _flush_records drops
+        # the steps that were skipped, which the reference never records (trans_sr_trainer.py:162-167)
+        keep = self.optimizer._dev_state.view(torch.int32)[4].clone() if self.device_guard else None
         if isinstance(rep, dict) and rep:
             for n in self.training_loss_names:
                 if n in rep:
                     v = rep.raw(n) if hasattr(rep, "raw") else dict.__getitem__(rep, n)
                     self._pending.setdefault(n, []).append(v.detach().clone() if torch.is_tensor(v) else float(v))
+                    self._pending_keep.setdefault(n, []).append(keep)
         elif len(self.training_loss_names) == 1:
             self._pending.setdefault(self.training_loss_names[0], []).append(loss.detach().clone())
+            self._pending_keep.setdefault(self.training_loss_names[0], []).append(keep)
         if sum(len(v) for v in self._pending.values()) >= self.RECORD_FLUSH:
             self._flush_records()
+
+    @staticmethod
+    def _filter_records(vals: list, keeps: list) -> list:
+        """The parked values of one loss component as floats, without the steps whose keep flag is 0 (a flag of None
+        keeps: the step ran without the device guard).  One copy for the values, one for the flags."""
+        ts = [v for v in vals if torch.is_tensor(v)]
+        host = torch.stack([t.reshape(()).float() for t in ts]).cpu().tolist() if ts else []
+        ks = [k for k in keeps if torch.is_tensor(k)]
+        flags = iter(torch.stack([k.reshape(()) for k in ks]).cpu().tolist() if ks else [])
+        it = iter(host)
+        out = []
+        for v, k in zip(vals, keeps):
+            x = next(it) if torch.is_tensor(v) else v
+            if (next(flags) if torch.is_tensor(k) else (1 if k is None else k)) != 0:
+                out.append(x)
+        return out
 
     def _flush_records(self) -> None:
         for n, vals in self._pending.items():
             if not vals:
                 continue
-            ts = [v for v in vals if torch.is_tensor(v)]
-            host = torch.stack([t.reshape(()).float() for t in ts]).cpu().tolist() if ts else []
-            it = iter(host)
-            self.training_loss_records.setdefault(n, []).extend(next(it) if torch.is_tensor(v) else v for v in vals)
+            keeps = self._pending_keep.get(n) or [None] * len(vals)
+            self.training_loss_records.setdefault(n, []).extend(self._filter_records(vals, keeps))
         self._pending = {}
+        self._pending_keep = {}
 
     def loss_records(self) -> Dict[str, list]:
         """``training_loss_records`` with every parked step converted (the reference reads the attribute directly,
@@ -151,6 +195,8 @@ class DPTrainStep:
             with (self.capture_hook() if self.capture_hook is not None else contextlib.nullcontext()):
                 with torch.cuda.graph(g):
                     self.fwd_bwd(*self._static)
+                    if self._update_in_graph():     # one linear chain on the capture stream: ..., backward, guard, Adam
+                        self._finish_step()
         except Exception as e:  # noqa: BLE001 - fall back to eager, loudly
             import warnings
             warnings.warn(f"rdst_amd.trainer: HIP-graph capture failed ({type(e).__name__}: {e}); running eagerly")
@@ -163,11 +209,13 @@ class DPTrainStep:
             dp._OFFERED = {}
             self.bucket.gather()
             self.use_graph, self.graph, self._static, self._graph_report = False, None, None, None
+            self._graph_has_update = False
             return False
         if not self.bucket.check_views():
             self.use_graph, self.graph, self._static, self._graph_report = False, None, None, None
             return False
         self.graph = g
+        self._graph_has_update = self._update_in_graph()
         # the report the capture produced: its tensors are the graph's own buffers, refreshed by every replay.  An eager
         # step in between (another shape) rebinds last_report to ITS tensors; step() re-points it before recording a replay.
         self._graph_report = self.last_report
@@ -182,7 +230,7 @@ class DPTrainStep:
         t0 = time.time()                               # :132
         self.current_epoch += 1                        # :134 — advanced whether or not the update is skipped
         self.net.train()
-        guarded = self.loss_threshold < GUARD_OFF
+        guarded = self.loss_threshold < GUARD_OFF and not self.device_guard
         if guarded:
             # the reference's order: forward, loss, decide, then backward (trans_sr_trainer.py:149-174); one host sync
             self.bucket.detach_grads()
@@ -207,11 +255,18 @@ class DPTrainStep:
             self.graph.replay()
             self.last_report = self._graph_report
             loss = self._loss_buf
+            in_graph = self._graph_has_update
         else:
             loss = self.fwd_bwd(inputs, targets)
             self._eager_seen += 1
-        self._record(loss)                             # :165-167 (lazy: no host sync)
-        self._finish_step()
+            in_graph = False
+        if self.device_guard:
+            if not in_graph:
+                self._finish_step()
+            self._record(loss)                         # after the guard: the decision is parked next to the loss
+        else:
+            self._record(loss)                         # :165-167 (lazy: no host sync)
+            self._finish_step()
         self.training_epoch_costs.append(time.time() - t0)   # :176-178 (host-side enqueue time: nothing synced)
         return loss
 
@@ -222,7 +277,8 @@ class DPTrainStep:
         has finished reading them.  Labels stay in the batch for the caller's own loop: ``step()`` takes none."""
         draw = sampler.draw()
         out = None
-        if self.graph is not None and self.loss_threshold >= GUARD_OFF and self._static is not None:
+        if (self.graph is not None and (self.device_guard or self.loss_threshold >= GUARD_OFF)
+                and self._static is not None):
             lr_shape, hr_shape = sampler.batch_shapes(draw)
             if (tuple(self._static[0].shape) == lr_shape and tuple(self._static[1].shape) == hr_shape
                     and self._static[0].dtype == torch.float32 and self._static[1].dtype == torch.float32
@@ -261,15 +317,45 @@ class DPTrainStep:
         self.quick_validation_reports.append(report)
         return report
 
+    def _collective(self) -> bool:
+        return (dist.is_available() and dist.is_initialized()
+                and (dist.get_world_size(self.group) > 1 or dp.FORCE_COLLECTIVES))
+
+    def _update_in_graph(self) -> bool:
+        """device_guard without collectives: guard and Adam take no per-step arguments, so they are captured too."""
+        return self.device_guard and not self._collective()
+
     def _finish_step(self) -> None:
+        if self.device_guard:
+            # _keep_step's rule without its .item(): any rank's skip (a NaN loss included) skips the whole group.  The flag
+            # is 4 bytes, computed and reduced on the device; the bucket all-reduce ALWAYS runs (its result is discarded on
+            # a skipped step) and the non-finite test sees the AVERAGED bucket, so every rank decides alike.
+            peer = None
+            if self._collective() and dist.get_world_size(self.group) > 1:
+                peer = torch.logical_not(self._loss_buf.double() < self.loss_threshold).to(torch.int32).reshape(1)
+                dist.all_reduce(peer, op=dist.ReduceOp.MAX, group=self.group)
+                self._peer_skip = peer
+            self.bucket.all_reduce_mean(self.group)
+            self.optimizer.guard(self._loss_buf, self.loss_threshold, max_grad_norm=self.max_grad_norm,
+                                 skip_nonfinite=self.skip_nonfinite, peer_skip=peer)
+            self.optimizer.step()                      # rdst_adam_step_dev: rate and step count come from the device
+            return
         self.bucket.all_reduce_mean(self.group)        # no-op on one rank
         self.optimizer.step()
         if self.scheduler is not None:
             self.scheduler.step()
 
+    def guard_stats(self) -> dict:
+        """The device guard's counters and latest decision (FlatAdam.sync_host(): one copy, the step's only read-back)."""
+        if not self.device_guard:
+            raise RuntimeError("DPTrainStep.guard_stats: needs device_guard=True")
+        return self.optimizer.sync_host()
+
     # ---- models/basic_trainer.py:164-208 -----------------------------------------------------------
     def checkpoint(self) -> dict:
         self._flush_records()
+        if self.device_guard:
+            self.optimizer.sync_host()                 # step count, rate and scheduler fields as `kept` updates leave them
         ck = {"Time": time.strftime("%Y-%m-%d %H:%M:%S"),
               "model_g": self.net.state_dict(),
               "optimizer_g": self.optimizer.state_dict(),
@@ -295,11 +381,20 @@ class DPTrainStep:
         self.optimizer.load_state_dict(ck["optimizer_g"])
         if self.scheduler is not None and "scheduler_g" in ck:
             self.scheduler.load_state_dict(ck["scheduler_g"])
+        if self.device_guard and self.scheduler is not None:
+            # the loaded schedule may differ from the constructor's: rebuild the rate table, and drop a graph that holds
+            # the old one by value (the next step captures again).  The step count went to the device in load_state_dict.
+            old = (self.optimizer._milestones, self.optimizer._lr_table)
+            self.optimizer.set_schedule(sorted(self.scheduler.milestones.elements()), self.scheduler.gamma,
+                                        base_lr=self.scheduler.base_lrs[0])
+            if old != (self.optimizer._milestones, self.optimizer._lr_table) and self._graph_has_update:
+                self.graph, self._static, self._graph_report, self._graph_has_update = None, None, None, False
         if "loss" in ck and len(ck["loss"]) and hasattr(self.loss_module, "load_state_dict"):
             self.loss_module.load_state_dict(ck["loss"])
         self.training_loss_names = ck.get("training_loss_names", self.training_loss_names)
         self.training_loss_records = ck.get("training_loss_records", self.training_loss_records)
         self._pending = {}             # steps taken before the load belong to the history that was just replaced
+        self._pending_keep = {}
         self.quick_validation_reports = ck.get("quick_validation_reports", [])
         self.current_training_state_id = ck.get("current_training_state_id", 0)
         self.current_epoch = ck.get("current_epoch", 0)
