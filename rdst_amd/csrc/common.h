@@ -51,6 +51,50 @@ static inline unsigned long long* rdst_stamps_begin(const char*, int, int, hipSt
 static inline void rdst_stamps_end(const char*, unsigned long long*, int, int, hipStream_t) {}
 #endif
 
+// The kernel side of the stamps: where a kernel's time goes, phase by phase.  Both fold to nothing when they are off.
+// RDST_PHASES_BEGIN(on) declares 8 cycle counters; RDST_PHASE(on, k) adds the cycles since the previous RDST_PHASE to counter k;
+// RDST_PHASES_STORE(cond, buf, row) writes them to row `row` of the buffer of rdst_stamps_begin().  `on` is RDST_DBGV(p.stamps)
+// (the constant 0 in the shipped library) or a constant set by a -D switch of the file.  (Macros, not a struct with methods:
+// the register-saturated kernels allocate differently around a struct, and a diagnostic build has to measure the shipped code.)
+#define RDST_PHASES_BEGIN(on)                                              \
+  unsigned long long tprev_ = (on) ? __builtin_readcyclecounter() : 0ull; \
+  unsigned long long tacc_[8] = {0, 0, 0, 0, 0, 0, 0, 0}
+#define RDST_PHASE(on, k)                                          \
+  if (on) {                                                        \
+    const unsigned long long tn_ = __builtin_readcyclecounter();   \
+    tacc_[k] += tn_ - tprev_;                                      \
+    tprev_ = tn_;                                                  \
+  }
+#define RDST_PHASES_STORE(cond, buf, row) \
+  if (cond)                               \
+    for (int k_ = 0; k_ < 8; ++k_) (buf)[(size_t)(row) * 8 + k_] = tacc_[k_]
+// WaveTicks<ON>: 8 counters per wave in clock64() ticks, without a buffer: lane 0 of every wave of workgroup 0 prints its 8 slots,
+// `legend` naming them.  ON is a -D switch of the file (tools/abl_build.sh); the kernel calls print() once, at its end.
+template <bool ON>
+struct WaveTicks {
+  long long tk[8], tl;
+  __device__ __forceinline__ WaveTicks() {
+    if constexpr (ON) {
+      for (int k = 0; k < 8; ++k) tk[k] = 0;
+      tl = clock64();
+    }
+  }
+  __device__ __forceinline__ void add(int k) {
+    if constexpr (ON) {
+      const long long n = clock64();
+      tk[k] += n - tl;
+      tl = n;
+    }
+  }
+  __device__ __forceinline__ void print(int wave, int lane, const char* role, const char* legend) const {
+    if constexpr (ON) {
+      if (blockIdx.x == 0 && lane == 0)
+        printf("wave %d %s [%s]: %lld %lld %lld %lld %lld %lld %lld %lld\n", wave, role, legend, tk[0], tk[1], tk[2], tk[3], tk[4],
+               tk[5], tk[6], tk[7]);
+    }
+  }
+};
+
 // thread-local last-error text behind rdst_last_error()
 extern thread_local char g_rdst_err[256];
 static inline int rdst_fail(int code, const char* fmt, ...) {
@@ -64,6 +108,17 @@ static inline int rdst_launch_status(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return rdst_fail(-(int)e, "%s: %s", what, hipGetErrorString(e));
   return 0;
+}
+
+// Launch `kern` with `smem` bytes of dynamic LDS and report the launch's status.  More than 64 KB of dynamic LDS has to be allowed per
+// kernel first, and that is done on EVERY launch: the attribute is per DEVICE, a process-wide "done" flag would leave a second GPU
+// without it.  At 64 KB or less the call is skipped — the limit it would set is the one every kernel starts with, so nothing the
+// runtime can observe changes (some kernels ask for less in their small instantiations).
+template <class K, class... A>
+static inline int rdst_launch(K kern, dim3 grid, dim3 threads, size_t smem, hipStream_t st, const char* what, const A&... args) {
+  if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  hipLaunchKernelGGL(kern, grid, threads, smem, st, args...);
+  return rdst_launch_status(what);
 }
 
 // The compute mode of an entry point's dtype, decoded first thing: `dtype` becomes the element type of the rows (RDST_BF16 or

@@ -28,6 +28,7 @@
 //                          two K halves exchange one accumulator tile each through LDS and finish one row each.
 // Everything else (fp32, other channel counts, W % 32 != 0, input activation) stays on conv_mfma.hip.
 #include "conv.h"
+#include "lds_dma.h"
 #include "mfma.h"
 #include "pack.h"
 #include <type_traits>
@@ -55,17 +56,11 @@ struct C3Args {
 
 };
 
-constexpr int pix_stride(int K) {  // bytes: >= 2K, multiple of 16, odd number of 16-B slots
-  int s = (2 * K + 15) / 16 * 16;
-  if (((s / 16) & 1) == 0) s += 16;
-  return s;
-}
-
 template <int K, int CW, int NT, int KSPLIT, int PSLOTS, int RPS, bool UNSHUF, bool PSTORE>
 struct C3Cfg {
   static constexpr int KSTEPS = (K + 15) / 16;
   static constexpr int KSH = (KSTEPS + KSPLIT - 1) / KSPLIT;
-  static constexpr int PSTRIDE = pix_stride(K);
+  static constexpr int PSTRIDE = lds_odd_stride(2 * K);   // a pixel: K bf16 channels
   static constexpr int SPP = PSTRIDE / 16;                 // 16-B slots per pixel
   static constexpr int RPIECES = (34 * SPP + 63) / 64;     // 1-KB LDS-DMA pieces per ring row
   static constexpr int ROWB = RPIECES * 1024;
@@ -92,22 +87,10 @@ __global__ void __launch_bounds__(256, 1) conv3_kernel(const C3Args p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int cg = wave % CW, kh = (wave / CW) % KSPLIT, ps = wave / (CW * KSPLIT);
   const int H = p.H, W = p.W;
-  unsigned long long tprev = RDST_DBGV(p.stamps) ? __builtin_readcyclecounter() : 0ull;
-  unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define STAMP_ADD(k)                                                   \
-  if (RDST_DBGV(p.stamps)) {                                           \
-    const unsigned long long tn_ = __builtin_readcyclecounter();       \
-    tacc[k] += tn_ - tprev;                                            \
-    tprev = tn_;                                                       \
-  }
+  RDST_PHASES_BEGIN(RDST_DBGV(p.stamps));
   // buffer descriptor of the input tensor (raw buffer, byte offsets, range = a_bytes: reads behind it return zeros), in SGPRs
-  typedef uint32_t u32x4s_t __attribute__((ext_vector_type(4)));
-  u32x4s_t rsrc;
-  rsrc.x = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)p.A);
-  rsrc.y = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)p.A >> 32) & 0xffffu);
-  rsrc.z = __builtin_amdgcn_readfirstlane((uint32_t)p.a_bytes);
-  rsrc.w = 0x00020000u;
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+  const u32x4s_t rsrc = dma_rsrc(p.A, (uint32_t)p.a_bytes);
+  const uint32_t lds0 = lds_base(smem);
 
   lds_zero16(smem, CF::BIAS_OFF, tid, 256);
   float* biasL = reinterpret_cast<float*>(smem + CF::BIAS_OFF);
@@ -151,13 +134,8 @@ __global__ void __launch_bounds__(256, 1) conv3_kernel(const C3Args p) {
     const int rowbase = UNSHUF ? (int)((((int64_t)sp.b * (2 * H) + 2 * y) * (int64_t)(2 * W)) * (p.lda * 2))
                                : (int)((((int64_t)sp.b * H + y) * W) * (p.lda * 2));
     const int off = (rowok && loff >= 0) ? rowbase + loff : p.a_bytes;   // out of range -> the DMA writes zeros
-    // Inline asm, not the builtin: the compiler orders every later ds_read behind a builtin LDS-DMA with s_waitcnt
-    // vmcnt(0) (it cannot tell that the slots differ), which exposes the whole HBM latency in every step.  The waits are
-    // placed by hand: vmcnt(0) after a step's MFMAs, in front of the barrier that publishes the rows.
-    const uint32_t ldst = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)((rel % NR) * ROWB + pi * 1024));
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(off), "s"(ldst), "s"(rsrc) : "memory");
+    // (no wait follows: vmcnt(0) is placed by hand after a step's MFMAs, in front of the barrier that publishes the rows)
+    lds_dma16(rsrc, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)((rel % NR) * ROWB + pi * 1024)), off);
   };
   auto first_rows = [&](const Strip& sp) {           // rel rows 0 .. RPS + 1
     for (int q = wave; q < (RPS + 2) * CF::RPIECES; q += 4) {
@@ -175,8 +153,7 @@ __global__ void __launch_bounds__(256, 1) conv3_kernel(const C3Args p) {
   // there) and only the rest live in VGPRs.
   constexpr int NFR = NT * 9 * KSH;
   constexpr int NA = NFR < CF::NA_MAX ? NFR : CF::NA_MAX, NV = NFR - NA;
-  typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-  u32x4_t wfa[NA > 0 ? NA : 1];
+  u32x4v_t wfa[NA > 0 ? NA : 1];
   Pack16 wfv[NV > 0 ? NV : 1];
   auto wsrc = [&](int f, bool& real) {
     const int t = f / (9 * KSH), rem = f - t * (9 * KSH), tap = rem / KSH, kk = rem - tap * KSH;
@@ -188,7 +165,7 @@ __global__ void __launch_bounds__(256, 1) conv3_kernel(const C3Args p) {
   for (int f = 0; f < NA; ++f) {
     bool real;
     const char* src = wsrc(f, real);
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=a"(wfa[f]) : "v"(src) : "memory");
+    frag_load_a(wfa[f], src);
   }
 #pragma unroll
   for (int f = 0; f < NV; ++f) {
@@ -196,27 +173,27 @@ __global__ void __launch_bounds__(256, 1) conv3_kernel(const C3Args p) {
     const u32x4_a4 v = *reinterpret_cast<const u32x4_a4*>(wsrc(NA + f, real));
     wfv[f].w[0] = real ? v.x : 0u; wfv[f].w[1] = real ? v.y : 0u; wfv[f].w[2] = real ? v.z : 0u; wfv[f].w[3] = real ? v.w : 0u;
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
 #pragma unroll
   for (int f = 0; f < NA; ++f) {
     bool real;
     (void)wsrc(f, real);
-    if (KSPLIT > 1 && !real) wfa[f] = u32x4_t{0u, 0u, 0u, 0u};
-    asm volatile("" : "+a"(wfa[f]));         // ordered behind the wait: every use of the fragment depends on this
+    if (KSPLIT > 1 && !real) wfa[f] = u32x4v_t{0u, 0u, 0u, 0u};
+    frag_pin_a(wfa[f]);         // ordered behind the wait: every use of the fragment depends on this
   }
   auto wfrag = [&](int t, int tap, int kk) {
     const int f = (t * 9 + tap) * KSH + kk;
     return f < NA ? __builtin_bit_cast(bf16x8_t, wfa[f < NA ? f : 0]) : __builtin_bit_cast(bf16x8_t, wfv[f < NA ? 0 : f - NA]);
   };
   __syncthreads();
-  STAMP_ADD(0);
+  RDST_PHASE(RDST_DBGV(p.stamps), 0);
   for (int strip = blockIdx.x; strip < p.nstrips; strip += gridDim.x) {
     const Strip sp = decode(strip);
     const int b = sp.b, y0 = sp.y0, x0 = sp.x0, nrows = sp.nrows;
     const int nsteps = (nrows + RPS - 1) / RPS;
     if (strip != (int)blockIdx.x) {
       first_rows(sp);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
       __syncthreads();
     }
     // the pieces this wave loads in every step: fixed (row-in-step, piece) pairs -> their lane offsets are loop invariants
@@ -224,7 +201,7 @@ __global__ void __launch_bounds__(256, 1) conv3_kernel(const C3Args p) {
     int loff[NPW];
 #pragma unroll
     for (int k = 0; k < NPW; ++k) loff[k] = lane_off(sp, (wave + 4 * k) % CF::RPIECES);
-    STAMP_ADD(1);
+    RDST_PHASE(RDST_DBGV(p.stamps), 1);
 
     for (int j = 0; j < nsteps; ++j) {
       const bool more = j + 1 < nsteps;
@@ -256,7 +233,7 @@ __global__ void __launch_bounds__(256, 1) conv3_kernel(const C3Args p) {
           }
         }
       }
-      STAMP_ADD(2);
+      RDST_PHASE(RDST_DBGV(p.stamps), 2);
 
       f32x16 acc[RPW][NT];
       bool live[RPW];
@@ -316,8 +293,8 @@ __global__ void __launch_bounds__(256, 1) conv3_kernel(const C3Args p) {
         }
       }
 
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the next step's rows have landed (issued >= half a step ago)
-      STAMP_ADD(3);
+      wait_vmcnt<0>();   // the next step's rows have landed (issued >= half a step ago)
+      RDST_PHASE(RDST_DBGV(p.stamps), 3);
       int fin = 0;                                        // the row (index into acc) this wave finishes
       if constexpr (KSPLIT == 2) {
         // the two K halves of a channel group hold partial sums of the same two rows: half kh gives away row 1 - kh
@@ -342,7 +319,7 @@ __global__ void __launch_bounds__(256, 1) conv3_kernel(const C3Args p) {
         fin = kh;
       }
 
-      STAMP_ADD(4);
+      RDST_PHASE(RDST_DBGV(p.stamps), 4);
       // ---- epilogue -------------------------------------------------------------------------------------------
 #pragma unroll
       for (int i = 0; i < (KSPLIT == 2 ? 1 : RPW); ++i) {
@@ -408,14 +385,12 @@ __global__ void __launch_bounds__(256, 1) conv3_kernel(const C3Args p) {
           }
         }
       }
-      STAMP_ADD(5);
+      RDST_PHASE(RDST_DBGV(p.stamps), 5);
       __syncthreads();
-      STAMP_ADD(6);
+      RDST_PHASE(RDST_DBGV(p.stamps), 6);
     }
   }
-  if (RDST_DBGV(p.stamps) && tid == 0)
-    for (int k = 0; k < 8; ++k) p.stamps[(size_t)blockIdx.x * 8 + k] = tacc[k];
-#undef STAMP_ADD
+  RDST_PHASES_STORE(RDST_DBGV(p.stamps) && tid == 0, p.stamps, blockIdx.x);
 }
 
 template <int K, int CW, int NT, int KSPLIT, int PSLOTS, int RPS, bool UNSHUF, bool PSTORE>
@@ -434,12 +409,10 @@ int launch_c3(C3Args& p, int ctile0, hipStream_t st, const char* what) {
   p.nstrips = (int)ns;
   const int grid = ns < 256 ? (int)ns : 256;
   auto kern = conv3_kernel<K, CW, NT, KSPLIT, PSLOTS, RPS, UNSHUF, PSTORE>;
-  // (per launch: the attribute is per DEVICE, a process-wide "done" flag would leave a second GPU without it)
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
   p.stamps = rdst_stamps_begin("RDST_C3_STAMPS", grid, 8, st);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), CF::SMEM, st, p);
+  const int rc = rdst_launch(kern, dim3((unsigned)grid), dim3(256), CF::SMEM, st, what, p);
   rdst_stamps_end(what, p.stamps, grid, 8, st);   // 0 weights, 1 first rows, 2 dma issue, 3 mfma, 4 exchange, 5 epilogue, 6 barrier
-  return rdst_launch_status(what);
+  return rc;
 }
 
 int pack(const float* Wc, bf16* out, int Cin, int Cout, int K, int N, int mode, float s, hipStream_t st) {

@@ -20,15 +20,10 @@
 // The old stripe kernel (conv_mfma.hip) split the taps over three workgroups per pixel range, read X and dY three
 // times and staged them through registers: 138 us average per launch for the same work.
 #include "conv.h"
+#include "lds_dma.h"
 #include "mfma.h"
 
 namespace {
-
-constexpr int lds_tr_stride(int bytes) {   // >= bytes, = 64 or 192 (mod 256)
-  int s = (bytes + 63) / 64 * 64;
-  while ((s % 256) != 64 && (s % 256) != 192) s += 64;
-  return s;
-}
 
 struct W3Args {
   const bf16* X; int64_t ldx; int x_bytes;
@@ -70,22 +65,8 @@ __global__ void __launch_bounds__(512, 2) conv3_wgrad_kernel(const W3Args p) {
   const int ctl = wave / CF::WPC, wq = wave % CF::WPC;      // channel tile inside the workgroup, chunk of its tiles
   const int ct = role * CF::CT + ctl;                       // channel tile of the (permuted) output channels
 
-  typedef uint32_t u32x4s_t __attribute__((ext_vector_type(4)));
-  auto make_rsrc = [&](const void* ptr, int bytes) {
-    u32x4s_t r;
-    r.x = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)ptr);
-    r.y = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)ptr >> 32) & 0xffffu);
-    r.z = __builtin_amdgcn_readfirstlane((uint32_t)bytes);
-    r.w = 0x00020000u;
-    return r;
-  };
-  const u32x4s_t rx = make_rsrc(p.X, p.x_bytes), ry = make_rsrc(p.dY, p.dy_bytes);
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  auto dma = [&](const u32x4s_t& rs, uint32_t ldst, int off) {   // inline asm: see conv3_mfma.hip
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(off), "s"(ldst), "s"(rs) : "memory");
-  };
+  const u32x4s_t rx = dma_rsrc(p.X, p.x_bytes), ry = dma_rsrc(p.dY, p.dy_bytes);
+  const uint32_t lds0 = lds_base(smem);
   lds_zero16(smem, CF::SMEM - 64, tid, 512);
   __syncthreads();
 
@@ -140,14 +121,14 @@ __global__ void __launch_bounds__(512, 2) conv3_wgrad_kernel(const W3Args p) {
     auto x_row = [&](int rel, int pi, int loff) {
       const int y = y0 - 1 + rel;
       const int rowbase = (int)((((int64_t)b * H + y) * W) * (p.ldx * 2));
-      dma(rx, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)((rel % CF::NRX) * CF::XROWB + pi * 1024)),
+      lds_dma16(rx, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)((rel % CF::NRX) * CF::XROWB + pi * 1024)),
           (y >= 0 && y < H && loff >= 0) ? rowbase + loff : p.x_bytes);
     };
     auto y_row = [&](int rel, int pi, int loff) {
       const int y = y0 + rel;
       const int rowbase = UNSHUF ? (int)((((int64_t)b * (2 * H) + 2 * y) * (int64_t)(2 * W)) * (p.lddy * 2))
                                  : (int)((((int64_t)b * H + y) * W) * (p.lddy * 2));
-      dma(ry, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::Y_OFF + (rel % CF::NRY) * CF::YROWB + pi * 1024)),
+      lds_dma16(ry, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::Y_OFF + (rel % CF::NRY) * CF::YROWB + pi * 1024)),
           (rel < nrows && loff >= 0) ? rowbase + loff : p.dy_bytes);
     };
     // a row set = X rows + dY rows of a step, pieces dealt round-robin to the 8 waves
@@ -165,7 +146,7 @@ __global__ void __launch_bounds__(512, 2) conv3_wgrad_kernel(const W3Args p) {
       }
     };
     load_set(0, RPS + 2, 0, RPS);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
 
     for (int j = 0; j < nsteps; ++j) {
@@ -203,7 +184,7 @@ __global__ void __launch_bounds__(512, 2) conv3_wgrad_kernel(const W3Args p) {
           }
         }
       }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
       __syncthreads();
     }
   }
@@ -276,14 +257,10 @@ int launch_w3(W3Args& p, float s, float* dW, float* dbias, hipStream_t st, const
   p.npg = ns < want ? (int)ns : want;
   const int grid = p.npg * CF::ROLES;
   auto kern = conv3_wgrad_kernel<CI, CO, UNSHUF>;
-  // (per launch: the attribute is per DEVICE, a process-wide "done" flag would leave a second GPU without it)
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), CF::SMEM, st, p);
-  if (int rc = rdst_launch_status(what)) return rc;
+  if (int rc = rdst_launch(kern, dim3((unsigned)grid), dim3(512), CF::SMEM, st, what, p)) return rc;
   const int tot = CF::ROLES * CF::SLABF / 2;
-  hipLaunchKernelGGL((conv3_wgrad_reduce_kernel<CI, CO, UNSHUF>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, p.slab,
-                     p.npg, s, dW, dbias);
-  return rdst_launch_status("conv3_wgrad_reduce");
+  return rdst_launch(conv3_wgrad_reduce_kernel<CI, CO, UNSHUF>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, "conv3_wgrad_reduce",
+                     p.slab, p.npg, s, dW, dbias);
 }
 
 bool rows_ok(const void* ptr, int64_t ld) { return ((uintptr_t)ptr & 3) == 0 && (ld & 1) == 0; }

@@ -15,15 +15,10 @@
 //     seen through a stride-2 pixel view of the shuffled tensor, output channels 4 c' + q;
 //   * fp32 slabs, summed in fixed order by conv3x_wgrad_reduce (deterministic), scale applied, scattered into (Cout, Cin, 3, 3).
 #include "conv.h"
+#include "lds_dma.h"
 #include "mfma.h"
 
 namespace {
-
-constexpr int lds_tr_stride(int bytes) {   // >= bytes, = 64 or 192 (mod 256)
-  int s = (bytes + 63) / 64 * 64;
-  while ((s % 256) != 64 && (s % 256) != 192) s += 64;
-  return s;
-}
 
 struct W3XArgs {
   const float* X; int64_t ldx; int x_bytes;
@@ -66,22 +61,8 @@ __global__ void __launch_bounds__(512, 2) conv3x_wgrad_kernel(const W3XArgs p) {
   const int pg = blockIdx.x;
   const int ct = wave / CF::WPC, wq = wave % CF::WPC;      // channel tile, chunk of its tiles
 
-  typedef uint32_t u32x4s_t __attribute__((ext_vector_type(4)));
-  auto make_rsrc = [&](const void* ptr, int bytes) {
-    u32x4s_t r;
-    r.x = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)ptr);
-    r.y = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)ptr >> 32) & 0xffffu);
-    r.z = __builtin_amdgcn_readfirstlane((uint32_t)bytes);
-    r.w = 0x00020000u;
-    return r;
-  };
-  const u32x4s_t rx = make_rsrc(p.X, p.x_bytes), ry = make_rsrc(p.dY, p.dy_bytes);
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  auto dma = [&](const u32x4s_t& rs, uint32_t ldst, int off) {   // inline asm: see conv3_mfma.hip
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(off), "s"(ldst), "s"(rs) : "memory");
-  };
+  const u32x4s_t rx = dma_rsrc(p.X, p.x_bytes), ry = dma_rsrc(p.dY, p.dy_bytes);
+  const uint32_t lds0 = lds_base(smem);
   lds_zero16(smem, CF::RAW_OFF, tid, 512);   // (the planes' pad columns / pixels)
   __syncthreads();
 
@@ -122,7 +103,7 @@ __global__ void __launch_bounds__(512, 2) conv3x_wgrad_kernel(const W3XArgs p) {
           const int sidx = q * 64 + lane, px = sidx / CF::RXSL, sl = sidx - px * CF::RXSL;
           const int x = x0 - 1 + px, y = y0 - 1 + xrel;
           const bool ok = x >= 0 && x < W && px < 34 && y >= 0 && y < H;
-          dma(rx, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::RAW_OFF + q * 1024)),
+          lds_dma16(rx, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::RAW_OFF + q * 1024)),
               ok ? (int)((((int64_t)b * H + y) * W + x) * (p.ldx * 4)) + sl * 16 : p.x_bytes);
         } else {
           const int q2 = q - npx;
@@ -130,7 +111,7 @@ __global__ void __launch_bounds__(512, 2) conv3x_wgrad_kernel(const W3XArgs p) {
           const int y = y0 + yrel;
           const bool ok = px < 32 && yrel < nrows;
           const int64_t mpix = ((int64_t)b * (H * p.ymul) + (int64_t)y * p.ymul + p.yoff) * ((int64_t)W * p.xmul) + (int64_t)(x0 + px) * p.xmul + p.xoff;
-          dma(ry, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::RAWY + q2 * 1024)), ok ? (int)(mpix * (p.lddy * 4)) + sl * 16 : p.dy_bytes);
+          lds_dma16(ry, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::RAWY + q2 * 1024)), ok ? (int)(mpix * (p.lddy * 4)) + sl * 16 : p.dy_bytes);
         }
       }
     };
@@ -166,7 +147,7 @@ __global__ void __launch_bounds__(512, 2) conv3x_wgrad_kernel(const W3XArgs p) {
 #pragma unroll 1
     for (int q = 0; q < 3; ++q) {
       load_raw(q, q == 2 ? 0 : -1);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
       __syncthreads();
       convert(q, q == 2 ? 0 : -1);
       __syncthreads();
@@ -216,7 +197,7 @@ __global__ void __launch_bounds__(512, 2) conv3x_wgrad_kernel(const W3XArgs p) {
           }
         }
       }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
       __syncthreads();   // the next step's raw rows are published; this step's plane reads are done
       if (more) {
         convert(j + 3, j + 1);
@@ -281,12 +262,9 @@ int launch_w3x(W3XArgs& p, float s, int cmul, int coff, float* dW, float* dbias,
   p.nstrips = (int)ns;
   p.npg = ns < 256 ? (int)ns : 256;
   auto kern = conv3x_wgrad_kernel<CI, CO>;
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
-  hipLaunchKernelGGL(kern, dim3((unsigned)p.npg), dim3(512), CF::SMEM, st, p);
-  if (int rc = rdst_launch_status(what)) return rc;
-  hipLaunchKernelGGL((conv3x_wgrad_reduce_kernel<CI, CO>), dim3((unsigned)((CF::SLABF + 255) / 256)), dim3(256), 0, st, p.slab, p.npg, s,
-                     CI, cmul, coff, dW, dbias);
-  return rdst_launch_status("conv3x_wgrad_reduce");
+  if (int rc = rdst_launch(kern, dim3((unsigned)p.npg), dim3(512), CF::SMEM, st, what, p)) return rc;
+  return rdst_launch(conv3x_wgrad_reduce_kernel<CI, CO>, dim3((unsigned)((CF::SLABF + 255) / 256)), dim3(256), 0, st, "conv3x_wgrad_reduce",
+                     p.slab, p.npg, s, CI, cmul, coff, dW, dbias);
 }
 
 }  // namespace

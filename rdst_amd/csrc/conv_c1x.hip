@@ -269,9 +269,7 @@ template <int C>
 int run_fwd(C1XArgs& p, hipStream_t st) {
   p.tiles_y = (p.H + TH1 - 1) / TH1;   // (this kernel's tiles are 4 rows high)
   p.ntiles = (int64_t)p.B * p.tiles_x * p.tiles_y;
-  (void)hipFuncSetAttribute((const void*)c1x_fwd_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fwd_smem<C>());
-  hipLaunchKernelGGL(c1x_fwd_kernel<C>, dim3(grid_of(p, 768)), dim3(NTHR), fwd_smem<C>(), st, p);
-  return rdst_launch_status("c1x_fwd");
+  return rdst_launch(c1x_fwd_kernel<C>, dim3(grid_of(p, 768)), dim3(NTHR), fwd_smem<C>(), st, "c1x_fwd", p);
 }
 template <int C>
 int run_wide(C1XArgs& p, hipStream_t st) {
@@ -281,9 +279,7 @@ int run_wide(C1XArgs& p, hipStream_t st) {
 template <int C>
 int run_wgrad(C1XArgs& p, float* dW, float* dbias, int wsc, int wst, int bias_wide, hipStream_t st) {
   const int grid = grid_of(p, 256), ROW = 10 * C + 1;
-  (void)hipFuncSetAttribute((const void*)c1x_wgrad_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_smem<C>());
-  hipLaunchKernelGGL(c1x_wgrad_kernel<C>, dim3(grid), dim3(NTHR), wg_smem<C>(), st, p);
-  if (int rc = rdst_launch_status("c1x_wgrad")) return rc;
+  if (int rc = rdst_launch(c1x_wgrad_kernel<C>, dim3(grid), dim3(NTHR), wg_smem<C>(), st, "c1x_wgrad", p)) return rc;
   float* red = p.slab + (size_t)grid * ROW;
   if (int rc = slab_reduce(p.slab, red, grid, ROW, st)) return rc;
   hipLaunchKernelGGL(c1x_wgrad_finish_kernel, dim3((ROW + 255) / 256), dim3(256), 0, st, red, C, p.s, wsc, wst, dW, dbias, bias_wide);

@@ -520,9 +520,7 @@ int launch_conv_rows(ConvArgs<T>& p, bool split, hipStream_t st, const char* wha
   auto kern = pf == 1 ? conv_rows_kernel<T, MODE, 1> : pf == 2 ? conv_rows_kernel<T, MODE, 2> : conv_rows_kernel<T, MODE, 3>;
   if constexpr (sizeof(T) == 4)
     if (split) kern = pf == 1 ? conv_rows_kernel<T, MODE, 1, true> : pf == 2 ? conv_rows_kernel<T, MODE, 2, true> : conv_rows_kernel<T, MODE, 3, true>;
-  if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, st, p);
-  return rdst_launch_status(what);
+  return rdst_launch(kern, dim3((unsigned)grid), dim3(512), smem, st, what, p);
 }
 
 template <typename T, int MODE>
@@ -552,17 +550,17 @@ int launch_conv(ConvArgs<T>& p, bool split, hipStream_t st, const char* what) {
   const int64_t nslabs = (p.g.pixels() + 31) / 32;
   int64_t grid = (nslabs + 7) / 8;
   if (grid > 256) grid = 256;
+  int rc = 0;
 #define RDST_CONV_LAUNCH(TM)                                                                                         \
   {                                                                                                                  \
     auto kern = conv_mfma_kernel<T, TM, MODE>;                                                                       \
     if constexpr (sizeof(T) == 4)                                                                                    \
       if (split) kern = conv_mfma_kernel<T, TM, MODE, true>;                                                         \
-    if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, st, p);                                          \
+    rc = rdst_launch(kern, dim3((unsigned)grid), dim3(512), smem, st, what, p);                                       \
   }
   if (p.Tn <= 4) RDST_CONV_LAUNCH(4) else if (p.Tn <= 8) RDST_CONV_LAUNCH(8) else RDST_CONV_LAUNCH(16)
 #undef RDST_CONV_LAUNCH
-  return rdst_launch_status(what);
+  return rc;
 }
 
 template <typename T> bool rows_ok(const void*, int64_t) { return true; }  // load_pack checks alignment per access
@@ -1222,17 +1220,17 @@ int conv_wgrad_mfma(const T* X, int64_t ldx, int in_act, const T* dYp, int64_t l
       p.pix_per_wg = (((P + nm - 1) / nm + SLr - 1) / SLr) * SLr;
       nm = (P + p.pix_per_wg - 1) / p.pix_per_wg;
       constexpr int PF = sizeof(T) == 2 ? 2 : 1;
+      int rc = 0;
 #define RDST_CR_LAUNCH(XF)                                                                                            \
       {                                                                                                              \
         auto kern = long_stripes ? conv_wgrad_rows_kernel<T, PF, XF, 128> : conv_wgrad_rows_kernel<T, PF, XF, 32>;  \
         if constexpr (sizeof(T) == 4)                                                                                \
           if (split) kern = long_stripes ? conv_wgrad_rows_kernel<T, PF, XF, 128, true> : conv_wgrad_rows_kernel<T, PF, XF, 32, true>; \
-        if (smem2 > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2); \
-        hipLaunchKernelGGL(kern, dim3((unsigned)nm, 3u), dim3(512), smem2, st, p);                                   \
+        rc = rdst_launch(kern, dim3((unsigned)nm, 3u), dim3(512), smem2, st, "conv_wgrad_rows", p);                   \
       }
       if (in_act) RDST_CR_LAUNCH(3) else RDST_CR_LAUNCH(0)
 #undef RDST_CR_LAUNCH
-      if (int rc = rdst_launch_status("conv_wgrad_rows")) return rc;
+      if (rc) return rc;
       const int64_t per_m = (int64_t)g.ks * g.Cout * g.ks * p.CinP;
       hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)((per_m + 255) / 256)), dim3(256), 0, st, slab, (int)nm, g,
                          p.CinP, p.ones_col, s, dW, dbias);
@@ -1247,9 +1245,7 @@ int conv_wgrad_mfma(const T* X, int64_t ldx, int in_act, const T* dYp, int64_t l
   p.pix_per_wg = (((P + nm - 1) / nm + CW_STRIPE - 1) / CW_STRIPE) * CW_STRIPE;
   nm = (P + p.pix_per_wg - 1) / p.pix_per_wg;
   auto kern = conv_wgrad_mfma_kernel<T>;
-  if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  hipLaunchKernelGGL(kern, dim3((unsigned)nm, (unsigned)g.ks), dim3(512), smem, st, p);
-  if (int rc = rdst_launch_status("conv_wgrad_mfma")) return rc;
+  if (int rc = rdst_launch(kern, dim3((unsigned)nm, (unsigned)g.ks), dim3(512), smem, st, "conv_wgrad_mfma", p)) return rc;
   const int64_t per_m = (int64_t)g.ks * g.Cout * g.ks * p.CinP;
   hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)((per_m + 255) / 256)), dim3(256), 0, st, slab, (int)nm, g,
                      p.CinP, p.ones_col, s, dW, dbias);

@@ -17,19 +17,13 @@
 // Shapes: K = 60 / 90 / 120 with N = 3K (norm1 + qkv), N = K (proj + shortcut), N = 30 (dense tail: LayerNorm +
 // Linear into the dense buffer).  Everything else stays on linear_mfma.hip.
 #include "linear.h"
+#include "lds_dma.h"
 #include "mfma.h"
 #include "pack.h"
 
 namespace {
 
 constexpr int L3_TT = 128;   // tokens per tile
-
-constexpr int l3_gcd(int a, int b) { return b == 0 ? a : l3_gcd(b, a % b); }
-constexpr int l3_stride(int K) {  // bytes: covers every k-step (no read leaves the token's row), odd number of 16-B slots
-  int s = (K + 15) / 16 * 32;
-  if (((s / 16) & 1) == 0) s += 16;
-  return s;
-}
 
 __global__ void __launch_bounds__(256) lin3_pack_kernel(const float* __restrict__ W, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, const float* __restrict__ bias,
@@ -52,7 +46,7 @@ constexpr int l3_nw(int NT) { return (NT >= 4 && NT <= 12) ? NT : 8; }
 template <int K, int NT, bool LN, bool RES>
 struct L3Cfg {
   static constexpr int KSTEPS = (K + 15) / 16;
-  static constexpr int XS = l3_stride(K), XSLOTS = XS / 16, XD = (2 * K + 15) / 16;
+  static constexpr int XS = lds_kstep_stride(K), XSLOTS = XS / 16, XD = (2 * K + 15) / 16;
   static constexpr int TP = (L3_TT * XSLOTS + 63) / 64, TILEB = TP * 1024;
   // residual tile (RES): [128 tokens][NT * 32 channels] bf16, 8 slots per 32 channels, + 1 slot: odd slot count
   static constexpr int RS = RES ? NT * 64 + 16 : 0, RSLOTS = RS / 16, RP = RES ? (L3_TT * RSLOTS + 63) / 64 : 0, RTILEB = RP * 1024;
@@ -64,7 +58,7 @@ struct L3Cfg {
   static constexpr int NW = l3_nw(NT);
   static constexpr int NTHR = 64 * NW;
   static constexpr int ITEMS = NT * 4, NJ = (ITEMS + NW - 1) / NW;
-  static constexpr int PERIOD = NT / l3_gcd(NW, NT), ND = NJ < PERIOD ? NJ : PERIOD;
+  static constexpr int PERIOD = NT / ce_gcd(NW, NT), ND = NJ < PERIOD ? NJ : PERIOD;
   static constexpr int CNT = (TP + NW - 1) / NW + (RES ? (RP + NW - 1) / NW : 0);   // DMA pieces per wave and tile
   static constexpr int R_OFF = NBUF * TILEB;
   static constexpr int STAT_OFF = R_OFF + NBUF * RTILEB;              // [NBUF][128][2] floats
@@ -85,29 +79,14 @@ __global__ void __launch_bounds__(64 * l3_nw(NT), l3_nw(NT) > 8 ? 1 : (2 * l3_nw
   float* statL = reinterpret_cast<float*>(smem + CF::STAT_OFF);
   const float* sbL = reinterpret_cast<const float*>(smem + CF::SB_OFF);
 
-  typedef uint32_t u32x4s_t __attribute__((ext_vector_type(4)));
-  auto make_rsrc = [&](const void* ptr, uint32_t bytes) {
-    u32x4s_t q;
-    q.x = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)ptr);
-    q.y = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)ptr >> 32) & 0xffffu);
-    q.z = __builtin_amdgcn_readfirstlane(bytes);
-    q.w = 0x00020000u;
-    return q;
-  };
-  const u32x4s_t rsx = make_rsrc(p.X, (uint32_t)p.x_bytes), rsr = make_rsrc(RES ? (const void*)p.R : (const void*)p.X, (uint32_t)p.r_bytes),
-                 rsb = make_rsrc(p.sb, 2 * NT * 32 * 4);
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  auto dma = [&](const u32x4s_t& rs, uint32_t ldst, int off) {   // inline asm: see conv3_mfma.hip
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(off), "s"(ldst), "s"(rs) : "memory");
-  };
+  const u32x4s_t rsx = dma_rsrc(p.X, (uint32_t)p.x_bytes), rsr = dma_rsrc(RES ? (const void*)p.R : (const void*)p.X, (uint32_t)p.r_bytes),
+                 rsb = dma_rsrc(p.sb, 2 * NT * 32 * 4);
+  const uint32_t lds0 = lds_base(smem);
   const int grid = gridDim.x;
   // ---- this wave's weight fragments: item j of the wave is (nt, tt) = ((wave + NW j) % NT, (wave + NW j) / NT) ------
   // Loaded BEFORE the tiles go in flight (memory operations retire in issue order, so every later wait for a tile also
   // covers them) and by inline asm: the compiler must not know about any load here, or it drains the whole queue
   // (vmcnt(0)) at the first use.  The same goes for spill reloads: the kernel must not spill.
-  typedef uint32_t u32x4v_t __attribute__((ext_vector_type(4)));
   u32x4v_t wfr[ND][KSTEPS];
 #pragma unroll
   for (int jd = 0; jd < ND; ++jd) {
@@ -115,13 +94,13 @@ __global__ void __launch_bounds__(64 * l3_nw(NT), l3_nw(NT) > 8 ? 1 : (2 * l3_nw
 #pragma unroll
     for (int ks = 0; ks < KSTEPS; ++ks) {
       const char* src = reinterpret_cast<const char*>(p.Wp) + (((int64_t)nt * KSTEPS + ks) * 64 + lane) * 16;
-      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(wfr[jd][ks]) : "v"(src) : "memory");
+      frag_load(wfr[jd][ks], src);
     }
   }
   {  // S / b' (2 x NT x 32 floats) by LDS-DMA as well: piece wave % NSBP (duplicates write the same bytes)
     constexpr int NSBP = (2 * NT * 32 * 4 + 1023) / 1024;
     const int pc = wave % NSBP;
-    dma(rsb, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::SB_OFF + pc * 1024)), pc * 1024 + lane * 16);
+    lds_dma16(rsb, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::SB_OFF + pc * 1024)), pc * 1024 + lane * 16);
   }
   // ---- a round = NBUF tiles, all in flight at once.  Every wave issues exactly CNT pieces per tile (a wave whose
   // share is one short repeats its last piece; tiles past the end are all-zero pieces), so "tile b has landed" is
@@ -140,7 +119,7 @@ __global__ void __launch_bounds__(64 * l3_nw(NT), l3_nw(NT) > 8 ? 1 : (2 * l3_nw
         const int tok = sidx / CF::XSLOTS, sl = sidx - tok * CF::XSLOTS;
         const int grow = tile * L3_TT + tok;
         const bool ok = tile < p.ntiles && tok < L3_TT && sl < CF::XD && grow < p.M;
-        dma(rsx, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(b * CF::TILEB + q * 1024)),
+        lds_dma16(rsx, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(b * CF::TILEB + q * 1024)),
             ok ? grow * ((int)p.ldx * 2) + sl * 16 : p.x_bytes);   // (extents < 2^31 bytes)
       }
       if constexpr (RES) {   // the residual rows of the tile: 16-B chunks of the N output channels
@@ -152,7 +131,7 @@ __global__ void __launch_bounds__(64 * l3_nw(NT), l3_nw(NT) > 8 ? 1 : (2 * l3_nw
           const int tok = sidx / CF::RSLOTS, sl = sidx - tok * CF::RSLOTS;
           const int grow = tile * L3_TT + tok;
           const bool ok = tile < p.ntiles && tok < L3_TT && sl * 8 < p.N && grow < p.M;
-          dma(rsr, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::R_OFF + b * CF::RTILEB + q * 1024)),
+          lds_dma16(rsr, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::R_OFF + b * CF::RTILEB + q * 1024)),
               ok ? grow * ((int)p.ldr * 2) + sl * 16 : p.r_bytes);
         }
       }
@@ -166,15 +145,15 @@ __global__ void __launch_bounds__(64 * l3_nw(NT), l3_nw(NT) > 8 ? 1 : (2 * l3_nw
       const int tile = tile0 + b * grid;
       if (tile >= p.ntiles) break;
       switch (NBUF - 1 - b) {   // the wait's count is an instruction immediate
-        case 3: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT * 3) : "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT * 2) : "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT * 1) : "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+        case 3: wait_vmcnt<CNT * 3>(); break;
+        case 2: wait_vmcnt<CNT * 2>(); break;
+        case 1: wait_vmcnt<CNT * 1>(); break;
+        default: wait_vmcnt<0>(); break;
       }
 #pragma unroll
       for (int jd = 0; jd < ND; ++jd)
 #pragma unroll
-        for (int ks = 0; ks < KSTEPS; ++ks) asm volatile("" : "+v"(wfr[jd][ks]));   // every use of a fragment is behind a wait
+        for (int ks = 0; ks < KSTEPS; ++ks) frag_pin(wfr[jd][ks]);   // every use of a fragment is behind a wait
       __syncthreads();
       const char* tb = smem + b * CF::TILEB;
       const char* rb = smem + CF::R_OFF + b * CF::RTILEB;
@@ -317,10 +296,7 @@ int launch_l3(L3Args& p, hipStream_t st, const char* what) {
   int grid = (p.ntiles + CF::NBUF - 1) / CF::NBUF;
   if (grid > 256 * CF::WGCU) grid = 256 * CF::WGCU;
   auto kern = lin3_kernel<K, NT, LN, RES>;
-  // (per launch: the attribute is per DEVICE, a process-wide "done" flag would leave a second GPU without it)
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(CF::NTHR), CF::SMEM, st, p);
-  return rdst_launch_status(what);
+  return rdst_launch(kern, dim3((unsigned)grid), dim3(CF::NTHR), CF::SMEM, st, what, p);
 }
 
 }  // namespace
@@ -363,11 +339,8 @@ int lin3_fwd_bf16(const bf16* X, int64_t ldx, const float* ln_w, const float* ln
   const int nt = (N + 31) / 32, ks = (K + 15) / 16;
   bf16* wp = reinterpret_cast<bf16*>(wpack);
   float* sb = reinterpret_cast<float*>(reinterpret_cast<char*>(wpack) + (size_t)nt * ks * 1024);
-  if (!prepacked) {
-    const int nfr = nt * ks * 64, nb1 = (nfr + 255) / 256, nb2 = (nt * 32 + 3) / 4;
-    hipLaunchKernelGGL(lin3_pack_kernel, dim3((unsigned)(nb1 + nb2)), dim3(256), 0, st, Wt, ln_w, ln_b, bias, wp, sb, N, K, ks, nt, s);
-    if (int rc = rdst_launch_status("lin3_pack")) return rc;
-  }
+  if (!prepacked)
+    if (int rc = lin3_pack_launch(Wt, ln_w, ln_b, bias, wpack, N, K, s, st)) return rc;
   L3Args p{};
   p.X = X; p.ldx = ldx; p.x_bytes = (int)xb; p.Wp = wp; p.sb = sb; p.R = R; p.ldr = ldr;
   p.r_bytes = R ? (int)(((M - 1) * ldr + N) * 2) : 0; p.Y = Y; p.ldy = ldy; p.stats = stats;

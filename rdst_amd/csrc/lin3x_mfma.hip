@@ -17,6 +17,7 @@
 // Shapes: K in {60, 90, 120} with N = 3K (norm1 + qkv), N = K + residual (proj), N = 30 (dense tails), N = 2K (norm2 + fc1), and
 // K = 2C, N = C with GELU on the way in + residual (fc2).  Everything else stays on linear_mfma.hip.
 #include "linear.h"
+#include "lds_dma.h"
 #include "mfma.h"
 #include "pack.h"
 
@@ -31,13 +32,9 @@
 
 // -DL3X_STAMPS: workgroup 0 prints, per wave, the clock64() ticks it spent in each phase of the tile loop (tools/abl_build.sh)
 #ifdef L3X_STAMPS
-#define L3X_T0 long long tk_[6] = {0, 0, 0, 0, 0, 0}, tl_ = clock64();
-#define L3X_T(i) { const long long n_ = clock64(); tk_[i] += n_ - tl_; tl_ = n_; }
-#define L3X_TP if (blockIdx.x == 0 && lane == 0) printf("wave %d: issue %lld  wait %lld  barrier1 %lld  convert %lld  barrier2 %lld  products+stores %lld\n", wave, tk_[0], tk_[1], tk_[2], tk_[3], tk_[4], tk_[5]);
+constexpr bool L3X_TICKS = true;
 #else
-#define L3X_T0
-#define L3X_T(i)
-#define L3X_TP
+constexpr bool L3X_TICKS = false;
 #endif
 
 namespace {
@@ -120,39 +117,24 @@ __global__ void __launch_bounds__((L3X<K, N, MODE, RES>::NTHR), (L3X<K, N, MODE,
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const float* bL = reinterpret_cast<const float*>(smem + CF::B_OFF);
 
-  typedef uint32_t u32x4s_t __attribute__((ext_vector_type(4)));
-  auto make_rsrc = [&](const void* ptr, uint32_t bytes) {
-    u32x4s_t q;
-    q.x = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)ptr);
-    q.y = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)ptr >> 32) & 0xffffu);
-    q.z = __builtin_amdgcn_readfirstlane(bytes);
-    q.w = 0x00020000u;
-    return q;
-  };
-  const u32x4s_t rsx = make_rsrc(p.X, (uint32_t)p.x_bytes), rsr = make_rsrc(RES ? (const void*)p.R : (const void*)p.X, (uint32_t)p.r_bytes),
-                 rsb = make_rsrc(p.bp, NT * 32 * 4);
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  auto dma = [&](const u32x4s_t& rs, uint32_t ldst, int off) {   // inline asm: see conv3_mfma.hip
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(off), "s"(ldst), "s"(rs) : "memory");
-  };
+  const u32x4s_t rsx = dma_rsrc(p.X, (uint32_t)p.x_bytes), rsr = dma_rsrc(RES ? (const void*)p.R : (const void*)p.X, (uint32_t)p.r_bytes),
+                 rsb = dma_rsrc(p.bp, NT * 32 * 4);
+  const uint32_t lds0 = lds_base(smem);
   const int grid = gridDim.x;
   // ---- this wave's weight fragments (hi, lo per 16 k) of output tile nt = wave % NT: inline-asm loads the compiler does not see, issued
   // before the tiles (memory operations retire in issue order: every later tile wait covers them).  The kernel must not spill.
-  typedef uint32_t u32x4v_t __attribute__((ext_vector_type(4)));
   u32x4v_t whi[KS], wlo[KS];
   const int nt = wave % NT;
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
     const char* src = reinterpret_cast<const char*>(p.Wp) + (((int64_t)nt * KS + ks) * 128 + lane) * 16;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(whi[ks]) : "v"(src) : "memory");
-    asm volatile("global_load_dwordx4 %0, %1, off offset:1024" : "=v"(wlo[ks]) : "v"(src) : "memory");
+    frag_load(whi[ks], src);
+    frag_load<1024>(wlo[ks], src);
   }
   {  // b' (NT x 32 floats) by LDS-DMA: piece wave % NBP (duplicates write the same bytes)
     constexpr int NBP = CF::BB / 1024;
     const int pc = wave % NBP;
-    dma(rsb, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::B_OFF + pc * 1024)), pc * 1024 + lane * 16);
+    lds_dma16(rsb, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::B_OFF + pc * 1024)), pc * 1024 + lane * 16);
   }
   // Every wave issues exactly CNT pieces per tile (a wave whose share is one short repeats its last piece; tiles past the end are
   // all-zero pieces): "the tile issued one iteration ago has landed" is the counted wait vmcnt(CNT) behind the NEXT tile's issue.
@@ -166,7 +148,7 @@ __global__ void __launch_bounds__((L3X<K, N, MODE, RES>::NTHR), (L3X<K, N, MODE,
       const int tok = sidx / CF::XSLOTS, sl = sidx - tok * CF::XSLOTS;
       const int grow = tile * TT + tok;
       const bool ok = tile < p.ntiles && tok < TT && sl < CF::XD && grow < p.M;
-      dma(rsx, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(b * CF::TILEB + q * 1024)),
+      lds_dma16(rsx, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(b * CF::TILEB + q * 1024)),
           ok ? grow * ((int)p.ldx * 4) + sl * 16 : p.x_bytes);   // (extents < 2^31 bytes)
     }
     if constexpr (RES) {
@@ -178,7 +160,7 @@ __global__ void __launch_bounds__((L3X<K, N, MODE, RES>::NTHR), (L3X<K, N, MODE,
         const int tok = sidx / CF::RSLOTS, sl = sidx - tok * CF::RSLOTS;
         const int grow = tile * TT + tok;
         const bool ok = tile < p.ntiles && tok < TT && sl < CF::RD && grow < p.M;
-        dma(rsr, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::R_OFF + b * CF::RTILEB + q * 1024)),
+        lds_dma16(rsr, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::R_OFF + b * CF::RTILEB + q * 1024)),
             ok ? grow * ((int)p.ldr * 4) + sl * 16 : p.r_bytes);
       }
     }
@@ -186,22 +168,22 @@ __global__ void __launch_bounds__((L3X<K, N, MODE, RES>::NTHR), (L3X<K, N, MODE,
 
   int b = 0;
   if ((int)blockIdx.x < p.ntiles) issue_tile(blockIdx.x, 0);
-  L3X_T0
+  WaveTicks<L3X_TICKS> wt;
   for (int tile = blockIdx.x; tile < p.ntiles; tile += grid, b ^= 1) {
     issue_tile(tile + grid, b ^ 1);   // (buffer b ^ 1: everybody left it at the barrier that ended the previous iteration)
-    L3X_T(0)
+    wt.add(0);
     // Wait for THIS tile (issued one iteration ago), not for what was issued since: the CNT pieces of the next tile and — the point —
     // the previous tile's output stores, which then drain beside this tile's conversion and products instead of in front of them
     // (a plain vmcnt(CNT) waits for them: memory operations complete in issue order).  The count must never exceed what really was
     // issued: a compute wave issues exactly 4 stores per item when N % 4 == 0 (no ragged chunk) and all rows lie below M — every
     // tile but the globally last one, which is the last of its workgroup; the first iteration has no stores behind it.
-    if (CF::NST > 0 && wave < NWC && tile != (int)blockIdx.x) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT + CF::NST) : "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT) : "memory");
+    if (CF::NST > 0 && wave < NWC && tile != (int)blockIdx.x) wait_vmcnt<CNT + CF::NST>();
+    else wait_vmcnt<CNT>();
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(whi[ks]), "+v"(wlo[ks]));   // every use of a fragment is behind a wait
-    L3X_T(1)
+    for (int ks = 0; ks < KS; ++ks) frag_pin(whi[ks], wlo[ks]);   // every use of a fragment is behind a wait
+    wt.add(1);
     __syncthreads();
-    L3X_T(2)
+    wt.add(2);
     char* tb = smem + b * CF::TILEB;
     char* rb = smem + CF::R_OFF + b * CF::RTILEB;
     // ---- conversion pass: raw fp32 row -> (LayerNorm | GELU | as it is) -> [8 hi | 8 hi | 8 lo | 8 lo] per 16 k, in place ----
@@ -277,9 +259,9 @@ __global__ void __launch_bounds__((L3X<K, N, MODE, RES>::NTHR), (L3X<K, N, MODE,
         }
       }
     }
-    L3X_T(3)
+    wt.add(3);
     __syncthreads();
-    L3X_T(4)
+    wt.add(4);
     // ---- items of this wave: output tile nt, token sub-tiles tt = (wave + NWC j) / NT ----
     if (wave < NWC) {
 #pragma unroll 1
@@ -375,11 +357,11 @@ __global__ void __launch_bounds__((L3X<K, N, MODE, RES>::NTHR), (L3X<K, N, MODE,
         }
       }
     }
-    L3X_T(5)
+    wt.add(5);
     __syncthreads();   // buffer b may be overwritten (the next iteration's issue targets it)
-    L3X_T(2)
+    wt.add(2);
   }
-  L3X_TP
+  wt.print(wave, lane, "", "issue wait barrier1 convert barrier2 products+stores - -");
 }
 
 template <int K, int N, int MODE, bool RES>
@@ -389,9 +371,7 @@ int launch_l3x(L3XArgs& p, hipStream_t st, const char* what) {
   const int cap = CF::TWO ? 512 : 256;
   int grid = p.ntiles < cap ? p.ntiles : cap;
   auto kern = lin3x_kernel<K, N, MODE, RES>;
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(CF::NTHR), CF::SMEM, st, p);
-  return rdst_launch_status(what);
+  return rdst_launch(kern, dim3((unsigned)grid), dim3(CF::NTHR), CF::SMEM, st, what, p);
 }
 
 __global__ void __launch_bounds__(256) lin3x_pack_kernel(const float* __restrict__ W, const float* __restrict__ gamma,

@@ -759,13 +759,13 @@ int launch_lin(LinArgs<T>& p, bool split, hipStream_t st, const char* what) {
     (void)hipMalloc((void**)&p.stamps, (size_t)grid * 16 * 8);
     (void)hipMemsetAsync(p.stamps, 0, (size_t)grid * 16 * 8, st);
   }
+  int rc = 0;
 #define RDST_LIN_LAUNCH(TM)                                                                                          \
   {                                                                                                                  \
     auto kern = lin_mfma_kernel<T, TM, MODE>;                                                                        \
     if constexpr (sizeof(T) == 4)                                                                                    \
       if (split) kern = lin_mfma_kernel<T, TM, MODE, true>;                                                          \
-    if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, st, p);                                          \
+    rc = rdst_launch(kern, dim3((unsigned)grid), dim3(512), smem, st, what, p);                                       \
   }
   if (p.Tn <= 8) RDST_LIN_LAUNCH(8) else if (p.Tn <= 16) RDST_LIN_LAUNCH(16) else RDST_LIN_LAUNCH(32)
 #undef RDST_LIN_LAUNCH
@@ -786,7 +786,7 @@ int launch_lin(LinArgs<T>& p, bool split, hipStream_t st, const char* what) {
     }
     free(hst);
   }
-  return rdst_launch_status(what);
+  return rc;
 }
 
 // ---- dgrad + LayerNorm backward, register-resident form -------------------------------------------
@@ -1392,15 +1392,15 @@ int linear_dgrad_ln_mfma(const T* X, int64_t ldx, const float* stats, const floa
   const int64_t cap = 256;   // persistent, one workgroup per CU (185+ VGPRs: a second one would not be resident anyway)
   if (grid > cap) grid = cap;
   *nslab = (int)grid;
+  int rc = 0;
 #define RDST_LND_LAUNCH(TM)                                                                                          \
   {                                                                                                                  \
     auto kern = lin_dgrad_ln_kernel<T, TM>;                                                                          \
-    if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, st, p);                                          \
+    rc = rdst_launch(kern, dim3((unsigned)grid), dim3(512), smem, st, "lin_dgrad_ln_mfma", p);                        \
   }
   if (p.Tn <= 8) RDST_LND_LAUNCH(8) else if (p.Tn <= 16) RDST_LND_LAUNCH(16) else RDST_LND_LAUNCH(32)
 #undef RDST_LND_LAUNCH
-  return rdst_launch_status("lin_dgrad_ln_mfma");
+  return rc;
 }
 
 int linear_wgrad_max_wgs(int N);
@@ -1448,18 +1448,18 @@ int wgrad_impl(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, co
   const int xf = lnfin ? 4 : ln_w ? 1 : in_act == RDST_ACT_GELU ? 2 : in_act ? 3 : 0;
   // plan size: packs per stripe over 512 threads (bf16 only; the fp32 parity mode keeps the general plan)
   const int sz = sizeof(T) != 2 ? 0 : (p.NT * 32 <= 128 && p.KT * 32 <= 128) ? 2 : (p.NT * 32 <= 256 && p.KT * 32 <= 128) ? 1 : 0;
+  int rc = 0;
 #define RDST_WG_LAUNCH(XF)                                                                                            \
   {                                                                                                                  \
     auto kern = sz == 2 ? lin_wgrad_mfma_kernel<T, PF, XF, 2> : sz == 1 ? lin_wgrad_mfma_kernel<T, PF, XF, 1>        \
                                                                          : lin_wgrad_mfma_kernel<T, PF, XF, 0>;      \
     if constexpr (sizeof(T) == 4)                                                                                    \
       if (split) kern = lin_wgrad_mfma_kernel<T, PF, XF, 0, true>;                                                   \
-    if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(WG_THREADS), smem, st, p);                                    \
+    rc = rdst_launch(kern, dim3((unsigned)nwg), dim3(WG_THREADS), smem, st, "lin_wgrad_mfma", p);                     \
   }
   if (xf == 0) RDST_WG_LAUNCH(0) else if (xf == 1) RDST_WG_LAUNCH(1) else if (xf == 2) RDST_WG_LAUNCH(2) else if (xf == 4) RDST_WG_LAUNCH(4) else RDST_WG_LAUNCH(3)
 #undef RDST_WG_LAUNCH
-  if (int rc = rdst_launch_status("lin_wgrad_mfma")) return rc;
+  if (rc) return rc;
   const int tot = N * p.Kx;
   if (lnfin) {
     rbatch::SumJob sj{};
@@ -1516,17 +1516,17 @@ int linear_dgrad_ln2_mfma(const T* X, int64_t ldx, const float* stats, const flo
   const int64_t nslabs = (M + 31) / 32;
   int64_t grid = (nslabs + 7) / 8;
   if (grid > 256) grid = 256;   // persistent, one workgroup per CU
+  int rc = 0;
 #define RDST_LND2_LAUNCH(NC)                                                                                          \
   {                                                                                                                  \
     auto kern = lin_dgrad_ln2_kernel<T, NC>;                                                                         \
     if constexpr (sizeof(T) == 4)                                                                                    \
       if (split) kern = lin_dgrad_ln2_kernel<T, NC, true>;                                                           \
-    if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, st, p);                                          \
+    rc = rdst_launch(kern, dim3((unsigned)grid), dim3(512), smem, st, "lin_dgrad_ln2_mfma", p);                       \
   }
   if (nct == 1) RDST_LND2_LAUNCH(1) else if (nct == 2) RDST_LND2_LAUNCH(2) else if (nct == 3) RDST_LND2_LAUNCH(3) else RDST_LND2_LAUNCH(4)
 #undef RDST_LND2_LAUNCH
-  return rdst_launch_status("lin_dgrad_ln2_mfma");
+  return rc;
 }
 
 #define INST(T)                                                                                                        \

@@ -14,6 +14,7 @@
 //     to LDS), every thread owning up to four 16-byte chunks of [dY | x | dX_add].
 // Same slab format (bf16, four rows per 8-byte store) and the same fixed-order reductions as the round-1 kernel.
 #include "linear.h"
+#include "lds_dma.h"
 #include "mfma.h"
 #include "wattn_hd.h"
 #include <stdlib.h>
@@ -31,14 +32,11 @@
 
 // -DLB3_STAMPS: workgroup 0 prints, per wave, the clock64() ticks it spent in each phase of the tile loop (tools/abl_build.sh)
 #ifdef LB3_STAMPS
-#define LB3_T0 long long tk_[5] = {0, 0, 0, 0, 0}, tl_ = clock64();
-#define LB3_T(i) { const long long n_ = clock64(); tk_[i] += n_ - tl_; tl_ = n_; }
-#define LB3_TP(role) if (blockIdx.x == 0 && lane == 0) printf("wave %d %s: stash %lld  fetch %lld  barrier %lld  compute %lld  finish %lld\n", wave, role, tk_[0], tk_[1], tk_[2], tk_[3], tk_[4]);
+constexpr bool LB3_TICKS = true;
 #else
-#define LB3_T0
-#define LB3_T(i)
-#define LB3_TP(role)
+constexpr bool LB3_TICKS = false;
 #endif
+constexpr const char* LB3_LEGEND = "stash fetch barrier compute finish - - -";
 
 namespace {
 using namespace wahd;
@@ -51,11 +49,6 @@ struct LB3Args {
   float* slab; int64_t slab_stride;
   int64_t M; int64_t ntiles; int tiles_per_wg;
 };
-
-__host__ __device__ constexpr int lb3_ldy(int NP) {   // dY tile row stride: odd 16-B slot count, not 16..47 (mod 256)
-  const int b = NP * 2 + 16;
-  return (b & 255) < 48 ? b + 64 : b;
-}
 
 template <int K_, int N_>
 struct LB3 {
@@ -86,7 +79,7 @@ struct LB3 {
   // (strides of 64 / 192 (mod 256) bytes — the four rows of a transposed read on disjoint bank quarters — were measured:
   // qkv / proj unchanged within noise, the tails 1-3 us slower (the 8-byte slice reads of the epilogue collide): not the limit)
   static constexpr int LDX = NCT == 4 ? 336 : CP * 2 + 16;
-  static constexpr int LDY = lb3_ldy(32 * NW);
+  static constexpr int LDY = lds_plane_stride(32 * NW);
   static constexpr int OFF_AC = 32 * LDX, OFF_DY = 64 * LDX, OFF_SM = OFF_DY + 32 * LDY, BUF = OFF_SM + 128;
   static constexpr int OFF_RED = 2 * BUF;
   static constexpr int SMEM = OFF_RED + 2 * NCT * 256;
@@ -227,15 +220,15 @@ __global__ void __launch_bounds__((LB3<K, N>::NT), (LB3<K, N>::WPS)) lnlin3_bwd_
 #pragma unroll
         for (int v = 0; v < 16; ++v) G[i][j][v] = 0.f;
     int b = 0;
-    LB3_T0
+    WaveTicks<LB3_TICKS> wt;
     for (int64_t tile = t0; tile < t1; ++tile, b ^= 1) {
       char* buf = smem + b * CF::BUF;
       ld.stash(p, tile, buf);
-      LB3_T(0)
+      wt.add(0);
       ld.fetch(p, tile + 1 < t1 ? tile + 1 : tile);   // every iteration defines the whole prefetch set
-      LB3_T(1)
+      wt.add(1);
       __syncthreads();   // the one barrier of the tile: buffer b staged; everybody is done with buffer b^1 and red[b]
-      LB3_T(2)
+      wt.add(2);
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         Pack16 ya[TN], xb[TC];
@@ -260,9 +253,9 @@ __global__ void __launch_bounds__((LB3<K, N>::NT), (LB3<K, N>::WPS)) lnlin3_bwd_
 #endif
           }
       }
-      LB3_T(3)
+      wt.add(3);
     }
-    LB3_TP("wgrad")
+    wt.print(wave, lane, "wgrad", LB3_LEGEND);
     if (LN) __syncthreads();
     // bf16 slab in groups of 4 rows (reduce_batch.h, "G4"): G [N][K+1]; p.slab_stride counts 8-byte groups
     uint2* my = reinterpret_cast<uint2*>(p.slab) + (int64_t)blockIdx.x * p.slab_stride;
@@ -358,17 +351,17 @@ __global__ void __launch_bounds__((LB3<K, N>::NT), (LB3<K, N>::WPS)) lnlin3_bwd_
     }
   };
   int b = 0;
-  LB3_T0
+  WaveTicks<LB3_TICKS> wt;
   for (int64_t tile = t0; tile < t1; ++tile, b ^= 1) {
     char* buf = smem + b * CF::BUF;
     ld.stash(p, tile, buf);
-    LB3_T(0)
+    wt.add(0);
     ld.fetch(p, tile + 1 < t1 ? tile + 1 : tile);
-    LB3_T(1)
+    wt.add(1);
     __syncthreads();
-    LB3_T(2)
+    wt.add(2);
     if (LN && prow >= 0) finish(b ^ 1);
-    LB3_T(4)
+    wt.add(4);
     const lds_cp yrow = (lds_cp)(buf + CF::OFF_DY + r * LDY + hh * 16);
 #pragma unroll
     for (int v = 0; v < 16; ++v) dx[v] = 0.f;
@@ -417,13 +410,13 @@ __global__ void __launch_bounds__((LB3<K, N>::NT), (LB3<K, N>::WPS)) lnlin3_bwd_
       s2 = half_swap_sum(s2);
       if (hh == 0) *reinterpret_cast<float2*>(red + ((b * NCT + dct) * 32 + r) * 2) = make_float2(s1, s2);
     } else {
-      LB3_T(3)
+      wt.add(3);
       finish(b);
-      LB3_T(4)
+      wt.add(4);
     }
-    LB3_T(3)
+    wt.add(3);
   }
-  LB3_TP("dgrad")
+  wt.print(wave, lane, "dgrad", LB3_LEGEND);
   if (LN) {
     __syncthreads();
     if (prow >= 0) finish(b ^ 1);
@@ -443,10 +436,8 @@ int lb3_launch(LB3Args& p, int64_t max_wgs, int* grid_out, hipStream_t st) {
   int64_t grid = p.ntiles < cap ? p.ntiles : cap;
   p.tiles_per_wg = (int)((p.ntiles + grid - 1) / grid);
   grid = (p.ntiles + p.tiles_per_wg - 1) / p.tiles_per_wg;
-  if (CF::SMEM > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(CF::NT), CF::SMEM, st, p);
   *grid_out = (int)grid;
-  return rdst_launch_status("lnlin3_bwd");
+  return rdst_launch(kern, dim3((unsigned)grid), dim3(CF::NT), CF::SMEM, st, "lnlin3_bwd", p);
 }
 
 }  // namespace

@@ -23,6 +23,7 @@
 // per lane) the host splits N in two launches over halves of the output features — LayerNorm backward is linear in dA — the
 // second accumulating onto the first's dX in place.
 #include "linear.h"
+#include "lds_dma.h"
 #include "mfma.h"
 #include "reduce_batch.h"
 #include "wattn_hd.h"
@@ -33,14 +34,11 @@
 
 // -DLBX_STAMPS: workgroup 0 prints, per wave, the clock64() ticks it spent in each phase of the tile loop (tools/abl_build.sh)
 #ifdef LBX_STAMPS
-#define LBX_T0 long long tk_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl_ = clock64();
-#define LBX_T(i) { const long long n_ = clock64(); tk_[i] += n_ - tl_; tl_ = n_; }
-#define LBX_TP(role) if (blockIdx.x == 0 && lane == 0) printf("wave %d %s: issue+wait %lld  barrierA %lld  finish_ln %lld  convert %lld  barrierB %lld  compute %lld (product %lld, rest %lld)\n", wave, role, tk_[0], tk_[1], tk_[2], tk_[3], tk_[4], tk_[5] + tk_[6] + tk_[7], tk_[6], tk_[7]);
+constexpr bool LBX_TICKS = true;
 #else
-#define LBX_T0
-#define LBX_T(i)
-#define LBX_TP(role)
+constexpr bool LBX_TICKS = false;
 #endif
+constexpr const char* LBX_LEGEND = "issue+wait barrierA finish_ln convert barrierB compute(wgrad) product(dgrad) rest(dgrad)";
 
 namespace {
 using namespace wahd;
@@ -54,11 +52,6 @@ struct LBXArgs {
   int64_t M; int64_t ntiles; int tiles_per_wg;
   int x_bytes, y_bytes;                // extents of X / dY (32-bit DMA offsets)
 };
-
-__host__ __device__ constexpr int lbx_ld(int cols) {   // plane row stride (bytes): odd 16-B slot count, not 16..47 (mod 256)
-  const int b = cols * 2 + 16;
-  return (b & 255) < 48 ? b + 64 : b;
-}
 
 // DT channel tiles per data-gradient wave, TN x TC accumulator tiles per weight-gradient wave
 template <int K_, int N_, int MODE_, int DT_, int TN_, int TC_>
@@ -80,7 +73,7 @@ struct LBX {
   static constexpr int NCV = 64 * NWG, TPR = NCV / 32, CKR = CKY + CKX, NJ = (CKR + TPR - 1) / TPR;
   static constexpr int RAW_X = TPY * 1024, RAW_S = RAW_X + TPX * 1024, RAWB = RAW_S + TPS * 1024;
   static constexpr int CP = 32 * NCT;
-  static constexpr int LDX = lbx_ld(CP), LDY = lbx_ld(32 * NW);
+  static constexpr int LDX = lds_plane_stride(CP), LDY = lds_plane_stride(32 * NW);
   static constexpr int OFF_XL = 32 * LDX, OFF_YH = 64 * LDX, OFF_YL = OFF_YH + 32 * LDY, OFF_SM = OFF_YL + 32 * LDY, PLB = OFF_SM + 128;   // the planes (one set) + rstd per row
   static constexpr int OFF_RED = (PLB + 15) / 16 * 16;
   // a data-gradient wave's bounce image: BR token rows x 32 floats (+ pad): dA leaves the registers (channel / lane = token) through it
@@ -142,26 +135,9 @@ __global__ void __launch_bounds__((CF::NT), (CF::WPS)) lnlin3x_bwd_kernel(const 
 
   // ---- raw rows by LDS-DMA, issued by the weight-gradient waves (CNT 1 KB pieces of a tile each; rows past M and the tail of a region
   // arrive as zeros or are never read).  A lane's offset inside a tile is the same for every tile: computed once.
-  typedef uint32_t u32x4s_t __attribute__((ext_vector_type(4)));
-  auto make_rsrc = [&](const void* ptr, uint32_t bytes) {
-    u32x4s_t v;
-    v.x = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)ptr);
-    v.y = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)ptr >> 32) & 0xffffu);
-    v.z = __builtin_amdgcn_readfirstlane(bytes);
-    v.w = 0x00020000u;
-    return v;
-  };
-  const u32x4s_t rsy = make_rsrc(p.dY, (uint32_t)p.y_bytes), rsx = make_rsrc(p.X, (uint32_t)p.x_bytes),
-                 rss = make_rsrc(MODE == BX_LN ? (const void*)p.stats : (const void*)p.X, MODE == BX_LN ? (uint32_t)(p.M * 8) : 0u);
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  auto dma = [&](const u32x4s_t& rs0, uint32_t ldst, int off) {   // inline asm: see conv3_mfma.hip
-    uint32_t keep;
-    u32x4s_t rs;   // (scalar again at the point of use: under SGPR pressure the descriptor otherwise arrives in vector registers)
-    rs.x = __builtin_amdgcn_readfirstlane(rs0.x); rs.y = __builtin_amdgcn_readfirstlane(rs0.y);
-    rs.z = __builtin_amdgcn_readfirstlane(rs0.z); rs.w = __builtin_amdgcn_readfirstlane(rs0.w);
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(off), "s"(ldst), "s"(rs) : "memory");
-  };
+  const u32x4s_t rsy = dma_rsrc(p.dY, (uint32_t)p.y_bytes), rsx = dma_rsrc(p.X, (uint32_t)p.x_bytes),
+                 rss = dma_rsrc(MODE == BX_LN ? (const void*)p.stats : (const void*)p.X, MODE == BX_LN ? (uint32_t)(p.M * 8) : 0u);
+  const uint32_t lds0 = lds_base(smem);
   int dmo[CF::CNT];
   if (is_wg) {
 #pragma unroll
@@ -188,9 +164,9 @@ __global__ void __launch_bounds__((CF::NT), (CF::WPS)) lnlin3x_bwd_kernel(const 
       const int pc = wave + NWG * i;
       if (pc >= CF::TPT) break;
       const uint32_t dst = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::OFF_RAW + b * CF::RAWB + pc * 1024));
-      if (pc < CF::TPY) dma(rsy, dst, dmo[i] + ty);
-      else if (pc < CF::TPY + CF::TPX) dma(rsx, dst, dmo[i] + tx);
-      else dma(rss, dst, dmo[i] + ts);
+      if (pc < CF::TPY) lds_dma16<true>(rsy, dst, dmo[i] + ty);
+      else if (pc < CF::TPY + CF::TPX) lds_dma16<true>(rsx, dst, dmo[i] + tx);
+      else lds_dma16<true>(rss, dst, dmo[i] + ts);
     }
   };
   // ---- the conversion pass of one tile (weight-gradient waves): raw chunk of 4 floats -> (x-hat | GELU | as it is) -> hi / lo into the
@@ -281,18 +257,18 @@ __global__ void __launch_bounds__((CF::NT), (CF::WPS)) lnlin3x_bwd_kernel(const 
 #pragma unroll
         for (int v = 0; v < 16; ++v) G[i][j][v] = 0.f;
     int b = 0;
-    LBX_T0
+    WaveTicks<LBX_TICKS> wt;
     for (int64_t tile = t0; tile < t1; ++tile, b ^= 1) {
       const char* buf = smem;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      LBX_T(0)
+      wait_vmcnt<0>();
+      wt.add(0);
       __syncthreads();   // raw tile landed (every wave's pieces); everybody is done with the planes and with raw buffer b ^ 1
-      LBX_T(1)
+      wt.add(1);
       issue_tile(tile + 1, b ^ 1);
       convert(b);
-      LBX_T(3)
+      wt.add(3);
       __syncthreads();   // planes staged
-      LBX_T(4)
+      wt.add(4);
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         Pack16 yh[TN], yl[TN];
@@ -320,9 +296,9 @@ __global__ void __launch_bounds__((CF::NT), (CF::WPS)) lnlin3x_bwd_kernel(const 
           }
         }
       }
-      LBX_T(5)
+      wt.add(5);
     }
-    LBX_TP("wgrad")
+    wt.print(wave, lane, "wgrad", LBX_LEGEND);
     if (LN) __syncthreads();   // (the data-gradient waves' closing barrier)
     // fp32 slab G [N][K+1] of this workgroup: consecutive lanes = consecutive channels of one row
     float* my = p.slab + (int64_t)blockIdx.x * p.slab_stride;
@@ -533,16 +509,16 @@ __global__ void __launch_bounds__((CF::NT), (CF::WPS)) lnlin3x_bwd_kernel(const 
     }
   };
   int b = 0;
-  LBX_T0
+  WaveTicks<LBX_TICKS> wt;
   for (int64_t tile = t0; tile < t1; ++tile, b ^= 1) {
     const char* buf = smem;
-    LBX_T(0)
+    wt.add(0);
     __syncthreads();
-    LBX_T(1)
+    wt.add(1);
     if constexpr (LN) {
       if (prow0 >= 0) finish_ln(b ^ 1);   // the previous tile's rows: every channel tile's partial sums are in `red` now
     }
-    LBX_T(2)
+    wt.add(2);
     // fc2: GELU'(pre-activation) of the wave's own channel tiles from the raw x tile, in the finish's row-wise layout — while the
     // weight-gradient waves convert (in the finish it was 5.8 of the 8.8 k cycles the data-gradient waves spent per tile)
     u32x4_a4 gp[MODE == BX_GELU ? DT : 1][4];
@@ -561,14 +537,14 @@ __global__ void __launch_bounds__((CF::NT), (CF::WPS)) lnlin3x_bwd_kernel(const 
         }
       }
     }
-    LBX_T(3)
+    wt.add(3);
     __syncthreads();
-    LBX_T(4)
+    wt.add(4);
     const int64_t row0 = tile * 32;
     if constexpr (LN) {
       load_runs(row0 + r, adp);   // consumed one tile later
       product(buf, 0, dxp);
-      LBX_T(6)
+      wt.add(6);
       prow0 = row0;
       // x-hat of the lane's own (token, channel) elements = hi + lo of the planes; partial row sums of this channel tile
       const lds_cp xrow = (lds_cp)(buf + r * LDX) + (32 * dwv + 4 * hh) * 2;
@@ -602,17 +578,17 @@ __global__ void __launch_bounds__((CF::NT), (CF::WPS)) lnlin3x_bwd_kernel(const 
           load_addends(row0, ct, adv);
         }
         product(buf, dt, dxv);
-        LBX_T(6)
+        wt.add(6);
         float o[16];
 #pragma unroll
         for (int v = 0; v < 16; ++v) o[v] = dxv[v];
         finish(o, adv, ct, row0);
-        LBX_T(7)
+        wt.add(7);
       }
     }
-    LBX_T(7)
+    wt.add(7);
   }
-  LBX_TP("dgrad")
+  wt.print(wave, lane, "dgrad", LBX_LEGEND);
   if constexpr (LN) {
     __syncthreads();   // (the last tile's partial sums)
     if (prow0 >= 0) finish_ln(b ^ 1);
@@ -630,10 +606,8 @@ int lbx_launch(LBXArgs& p, int64_t max_wgs, int* grid_out, hipStream_t st) {
   p.tiles_per_wg = (int)((p.ntiles + grid - 1) / grid);
   grid = (p.ntiles + p.tiles_per_wg - 1) / p.tiles_per_wg;
   p.slab_stride = (int64_t)N * (K + 1);
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(CF::NT), CF::SMEM, st, p);
   *grid_out = (int)grid;
-  return rdst_launch_status("lnlin3x_bwd");
+  return rdst_launch(kern, dim3((unsigned)grid), dim3(CF::NT), CF::SMEM, st, "lnlin3x_bwd", p);
 }
 
 // one launch over output features [n0, n0 + NN) of a Linear with N outputs in all (NN = N: the whole layer)

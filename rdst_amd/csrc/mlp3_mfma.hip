@@ -11,6 +11,7 @@
 // token): ~16 us at C = 120 against 65 us for the LDS-weight kernel of mlp_mfma.hip it replaces.
 // C = 60 / 90 / 120 with hid = 2 C; everything else stays on mlp_mfma.hip.
 #include "linear.h"
+#include "lds_dma.h"
 #include "mfma.h"
 
 #ifndef M3_ABL
@@ -21,12 +22,6 @@ namespace {
 
 constexpr int M3_TT = 128;
 
-constexpr int m3_gcd(int a, int b) { return b == 0 ? a : m3_gcd(b, a % b); }
-constexpr int m3_stride(int K) {  // bytes: covers every k-step, odd number of 16-B slots
-  int s = (K + 15) / 16 * 32;
-  if (((s / 16) & 1) == 0) s += 16;
-  return s;
-}
 
 struct M3Args {
   const bf16* X; int64_t ldx; int x_bytes;
@@ -50,13 +45,13 @@ struct M3Cfg {
   static constexpr int HID = 2 * C;
   static constexpr int KS1 = (C + 15) / 16, NT1 = (HID + 31) / 32;
   static constexpr int KS2 = (HID + 15) / 16, NT2 = (C + 31) / 32;
-  static constexpr int XS = m3_stride(C), XSLOTS = XS / 16, XD = (2 * C + 15) / 16;
+  static constexpr int XS = lds_kstep_stride(C), XSLOTS = XS / 16, XD = (2 * C + 15) / 16;
   static constexpr int TP = (M3_TT * XSLOTS + 63) / 64, TILEB = TP * 1024;
-  static constexpr int HS = m3_stride(HID), HTILEB = M3_TT * HS;
+  static constexpr int HS = lds_kstep_stride(HID), HTILEB = M3_TT * HS;
   // waves: a divisor arrangement in which every wave owns ONE hidden tile and ONE output tile (one fragment set each)
   static constexpr int NW = m3_nw(C), NTHR = 64 * NW;
-  static constexpr int NJ1 = (NT1 * 4 + NW - 1) / NW, P1 = NT1 / m3_gcd(NW, NT1), ND1 = NJ1 < P1 ? NJ1 : P1;
-  static constexpr int NJ2 = (NT2 * 4 + NW - 1) / NW, P2 = NT2 / m3_gcd(NW, NT2), ND2 = NJ2 < P2 ? NJ2 : P2;
+  static constexpr int NJ1 = (NT1 * 4 + NW - 1) / NW, P1 = NT1 / ce_gcd(NW, NT1), ND1 = NJ1 < P1 ? NJ1 : P1;
+  static constexpr int NJ2 = (NT2 * 4 + NW - 1) / NW, P2 = NT2 / ce_gcd(NW, NT2), ND2 = NJ2 < P2 ? NJ2 : P2;
   static constexpr int NBUF = 2;
   static constexpr int CNT = (TP + NW - 1) / NW;
   static constexpr int H_OFF = NBUF * TILEB;
@@ -88,33 +83,11 @@ __global__ void __launch_bounds__(64 * m3_nw(C), M3Cfg<C>::WGCU == 2 ? (2 * m3_n
   gelu_tab4_fill(smem + CF::TAB_OFF, tid, CF::NTHR);   // visible after the first tile's barrier
   const char* gtab = smem + CF::TAB_OFF;
 
-  typedef uint32_t u32x4s_t __attribute__((ext_vector_type(4)));
-  auto make_rsrc = [&](const void* ptr, uint32_t bytes) {
-    u32x4s_t q;
-    q.x = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)ptr);
-    q.y = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)ptr >> 32) & 0xffffu);
-    q.z = __builtin_amdgcn_readfirstlane(bytes);
-    q.w = 0x00020000u;
-    return q;
-  };
-  const u32x4s_t rsx = make_rsrc(p.X, (uint32_t)p.x_bytes), rs1 = make_rsrc(p.sb1, 2 * NT1 * 32 * 4), rs2 = make_rsrc(p.sb2, 2 * NT2 * 32 * 4);
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  auto dma = [&](const u32x4s_t& rs, uint32_t ldst, int off) {   // inline asm: see conv3_mfma.hip
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(off), "s"(ldst), "s"(rs) : "memory");
-  };
+  const u32x4s_t rsx = dma_rsrc(p.X, (uint32_t)p.x_bytes), rs1 = dma_rsrc(p.sb1, 2 * NT1 * 32 * 4), rs2 = dma_rsrc(p.sb2, 2 * NT2 * 32 * 4);
+  const uint32_t lds0 = lds_base(smem);
   const int grid = gridDim.x;
-  unsigned long long tprev = RDST_DBGV(p.stamps) ? __builtin_readcyclecounter() : 0ull;
-  unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define STAMP_ADD(k)                                                   \
-  if (RDST_DBGV(p.stamps)) {                                           \
-    const unsigned long long tn_ = __builtin_readcyclecounter();       \
-    tacc[k] += tn_ - tprev;                                            \
-    tprev = tn_;                                                       \
-  }
+  RDST_PHASES_BEGIN(RDST_DBGV(p.stamps));
   // ---- weight fragments (inline-asm loads, issued before the tiles: see lin3_mfma.hip) ---------------------------
-  typedef uint32_t u32x4v_t __attribute__((ext_vector_type(4)));
   u32x4v_t w1[ND1][KS1], w2[ND2][KS2];
 #pragma unroll
   for (int jd = 0; jd < ND1; ++jd) {
@@ -122,7 +95,7 @@ __global__ void __launch_bounds__(64 * m3_nw(C), M3Cfg<C>::WGCU == 2 ? (2 * m3_n
 #pragma unroll
     for (int ks = 0; ks < KS1; ++ks) {
       const char* src = reinterpret_cast<const char*>(p.W1p) + (((int64_t)nt * KS1 + ks) * 64 + lane) * 16;
-      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(w1[jd][ks]) : "v"(src) : "memory");
+      frag_load(w1[jd][ks], src);
     }
   }
 #pragma unroll
@@ -131,14 +104,14 @@ __global__ void __launch_bounds__(64 * m3_nw(C), M3Cfg<C>::WGCU == 2 ? (2 * m3_n
 #pragma unroll
     for (int ks = 0; ks < KS2; ++ks) {
       const char* src = reinterpret_cast<const char*>(p.W2p) + (((int64_t)nt * KS2 + ks) * 64 + lane) * 16;
-      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(w2[jd][ks]) : "v"(src) : "memory");
+      frag_load(w2[jd][ks], src);
     }
   }
   {  // S / b' of both layers by LDS-DMA: every wave one piece of each (duplicates write the same bytes)
     constexpr int N1P = CF::SB1_B / 1024, N2P = CF::SB2_B / 1024;
     const int p1 = wave % N1P, p2 = wave % N2P;
-    dma(rs1, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::SB1_OFF + p1 * 1024)), p1 * 1024 + lane * 16);
-    dma(rs2, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::SB2_OFF + p2 * 1024)), p2 * 1024 + lane * 16);
+    lds_dma16(rs1, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::SB1_OFF + p1 * 1024)), p1 * 1024 + lane * 16);
+    lds_dma16(rs2, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::SB2_OFF + p2 * 1024)), p2 * 1024 + lane * 16);
   }
   auto issue_tile = [&](int tile, int b) {   // exactly CNT pieces per wave
 #pragma unroll
@@ -149,7 +122,7 @@ __global__ void __launch_bounds__(64 * m3_nw(C), M3Cfg<C>::WGCU == 2 ? (2 * m3_n
       const int tok = sidx / CF::XSLOTS, sl = sidx - tok * CF::XSLOTS;
       const int grow = tile * M3_TT + tok;
       const bool ok = tile < p.ntiles && tok < M3_TT && sl < CF::XD && grow < p.M;
-      dma(rsx, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(b * CF::TILEB + q * 1024)),
+      lds_dma16(rsx, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(b * CF::TILEB + q * 1024)),
           ok ? grow * ((int)p.ldx * 2) + sl * 16 : p.x_bytes);   // (extent < 2^31 bytes)
     }
   };
@@ -165,18 +138,18 @@ __global__ void __launch_bounds__(64 * m3_nw(C), M3Cfg<C>::WGCU == 2 ? (2 * m3_n
   int kk = 0;
   for (int tile = blockIdx.x; tile < p.ntiles; tile += grid, ++kk) {
     const int b = kk & 1;
-    if (kk == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT) : "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT + NST) : "memory");
+    if (kk == 0) wait_vmcnt<CNT>();
+    else wait_vmcnt<CNT + NST>();
 #pragma unroll
     for (int jd = 0; jd < ND1; ++jd)
 #pragma unroll
-      for (int ks = 0; ks < KS1; ++ks) asm volatile("" : "+v"(w1[jd][ks]));
+      for (int ks = 0; ks < KS1; ++ks) frag_pin(w1[jd][ks]);
 #pragma unroll
     for (int jd = 0; jd < ND2; ++jd)
 #pragma unroll
-      for (int ks = 0; ks < KS2; ++ks) asm volatile("" : "+v"(w2[jd][ks]));
+      for (int ks = 0; ks < KS2; ++ks) frag_pin(w2[jd][ks]);
     __syncthreads();   // B0: tile landed (and: every wave is done with the previous tile's h)
-    STAMP_ADD(0);
+    RDST_PHASE(RDST_DBGV(p.stamps), 0);
     const char* tb = smem + b * CF::TILEB;
     float* st = statL + b * M3_TT * 2;
     for (int tok = tid >> 2; tok < M3_TT; tok += CF::NTHR / 4) {  // (mean, rstd): 4 lanes per token, two passes over the row's 16-B slots
@@ -221,7 +194,7 @@ __global__ void __launch_bounds__(64 * m3_nw(C), M3Cfg<C>::WGCU == 2 ? (2 * m3_n
       }
     }
     __syncthreads();   // B1: statistics visible
-    STAMP_ADD(1);
+    RDST_PHASE(RDST_DBGV(p.stamps), 1);
     // ---- phase 1: h = GELU(LN(x) W1^T + b1) -> LDS -----------------------------------------------------------
 #pragma unroll
     for (int jd = 0; jd < ND1; ++jd)
@@ -281,9 +254,9 @@ __global__ void __launch_bounds__(64 * m3_nw(C), M3Cfg<C>::WGCU == 2 ? (2 * m3_n
           if (n0 * 2 + 8 <= HS) *reinterpret_cast<u32x2_a4*>(hrow + n0 * 2) = uu;   // (padded hidden units past the row are dropped)
         }
       }
-    STAMP_ADD(2);
+    RDST_PHASE(RDST_DBGV(p.stamps), 2);
     __syncthreads();   // B2: h complete
-    STAMP_ADD(3);
+    RDST_PHASE(RDST_DBGV(p.stamps), 3);
     // ---- phase 2: y = x + h W2^T + b2 -------------------------------------------------------------------------
 #pragma unroll
     for (int jd = 0; jd < ND2; ++jd)
@@ -344,14 +317,12 @@ __global__ void __launch_bounds__(64 * m3_nw(C), M3Cfg<C>::WGCU == 2 ? (2 * m3_n
           }
         }
       }
-    STAMP_ADD(4);
+    RDST_PHASE(RDST_DBGV(p.stamps), 4);
     __syncthreads();   // B3: the x tile (residual reads) and h are free: buffer b may take tile k + 2
     issue_tile(tile + 2 * grid, b);
-    STAMP_ADD(5);
+    RDST_PHASE(RDST_DBGV(p.stamps), 5);
   }
-  if (RDST_DBGV(p.stamps) && tid == 0)
-    for (int k = 0; k < 8; ++k) p.stamps[(size_t)blockIdx.x * 8 + k] = tacc[k];
-#undef STAMP_ADD
+  RDST_PHASES_STORE(RDST_DBGV(p.stamps) && tid == 0, p.stamps, blockIdx.x);
 }
 
 template <int C>
@@ -362,12 +333,10 @@ int launch_m3(M3Args& p, hipStream_t st) {
   if (grid > 256 * CF::WGCU) grid = 256 * CF::WGCU;
   if (grid < 1) grid = 1;
   auto kern = mlp3_fwd_kernel<C>;
-  // (per launch: the attribute is per DEVICE, a process-wide "done" flag would leave a second GPU without it)
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
   p.stamps = rdst_stamps_begin("RDST_M3_STAMPS", grid, 8, st);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(CF::NTHR), CF::SMEM, st, p);
+  const int rc = rdst_launch(kern, dim3((unsigned)grid), dim3(CF::NTHR), CF::SMEM, st, "mlp3_fwd", p);
   rdst_stamps_end("mlp3_fwd: 0 wait+B0, 1 stats, 2 phase 1, 3 wait+B2, 4 phase 2, 5 B3+issue", p.stamps, grid, 8, st);
-  return rdst_launch_status("mlp3_fwd");
+  return rc;
 }
 
 }  // namespace

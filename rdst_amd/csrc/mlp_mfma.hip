@@ -1285,12 +1285,12 @@ extern "C" int rdst_mlp_bwd(const void* X, int64_t ld_x, const float* ln_w, cons
   // bf16 G4 slabs: (hid/4) x (C+1) groups of region 1 + (hid/4 + 1) x C groups of region 2, 8 bytes each (2 floats)
   p.slab_stride = (int64_t)((hid + 3) / 4) * (C + 1) + (int64_t)((hid + 4) / 4) * C;
   float* G = p.slab + 512 * ((int64_t)hid * (C + 1) + (int64_t)(hid + 1) * C);   // (behind the fp32-sized slab region)
+  int rc = 0;
 #define RDST_MLPB(NC)                                                                                                \
   {                                                                                                                  \
     auto kern = split ? mlp_bwd_kernel<NC, true> : mlp_bwd_kernel<NC, false>;                                                                                \
     constexpr int smem = MlpCfg<NC>::SMEM;                                                                           \
-    if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem); \
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(128 * NC), smem, st, p);                                     \
+    rc = rdst_launch(kern, dim3((unsigned)grid), dim3(128 * NC), smem, st, "mlp_bwd", p);                             \
   }
   static int split = -1;
   if (split < 0) { const char* e = rdst_dbg_getenv("RDST_MLP_SPLIT"); split = (e && e[0] == '1') ? 1 : 0; }
@@ -1320,7 +1320,7 @@ extern "C" int rdst_mlp_bwd(const void* X, int64_t ld_x, const float* ln_w, cons
     }
     free(hst);
   }
-  if (int rc = rdst_launch_status("mlp_bwd")) return rc;
+  if (rc) return rc;
   const int tot = (int)p.slab_stride;
   {
     (void)tot;
@@ -1370,13 +1370,13 @@ extern "C" int rdst_mlp_fwd(const void* X, int64_t ld_x, const float* ln_w, cons
   int64_t grid = p.ntiles < cap ? p.ntiles : cap;
   p.tiles_per_wg = (int)((p.ntiles + grid - 1) / grid);
   grid = (p.ntiles + p.tiles_per_wg - 1) / p.tiles_per_wg;
+  int rc = 0;
 #define RDST_MLPF(NC)                                                                                                \
   {                                                                                                                  \
     auto kern = mlp_fwd_kernel<NC>;                                                                                  \
     const int smem = MlpFwdCfg<NC>::smem(hid, C);                                                                    \
     if (smem > 160 * 1024) return RDST_ENOTSUP;                                                                      \
-    if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem); \
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(128 * NC), smem, st, p);                                     \
+    rc = rdst_launch(kern, dim3((unsigned)grid), dim3(128 * NC), smem, st, "mlp_fwd", p);                             \
   }
   static int want_stamps = -1;
   if (want_stamps < 0) { const char* e = rdst_dbg_getenv("RDST_MLPF_STAMPS"); want_stamps = e ? atoi(e) : 0; }
@@ -1403,7 +1403,7 @@ extern "C" int rdst_mlp_fwd(const void* X, int64_t ld_x, const float* ln_w, cons
     }
     free(hst);
   }
-  return rdst_launch_status("mlp_fwd");
+  return rc;
 }
 
 int wgrad_reduce_launch(const float* slab, int nwg, int N, int K, float s, float* dW, float* dbias, hipStream_t st);
@@ -1481,11 +1481,11 @@ int linear_ln_bwd_fused_bf16(const bf16* X, int64_t ldx, const float* ln_w, cons
   grid = (p.ntiles + p.tiles_per_wg - 1) / p.tiles_per_wg;
   p.slab = slab;
   p.slab_stride = (int64_t)((N + 3) / 4) * (K + 1);   // bf16 G4 slab: 8-byte groups
+  int rc = 0;
 #define RDST_LNLIN(NC)                                                                                               \
   {                                                                                                                  \
     auto kern = ln ? lnlin_bwd_kernel<NC, true> : lnlin_bwd_kernel<NC, false>;                                       \
-    if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem); \
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), smem, st, p);                                           \
+    rc = rdst_launch(kern, dim3((unsigned)grid), dim3(NT), smem, st, "lnlin_bwd", p);                                 \
   }
   static int want_stamps = -1;
   if (want_stamps < 0) { const char* e = rdst_dbg_getenv("RDST_LNLIN_STAMPS"); want_stamps = e ? atoi(e) : 0; }
@@ -1512,6 +1512,6 @@ int linear_ln_bwd_fused_bf16(const bf16* X, int64_t ldx, const float* ln_w, cons
     }
     free(hst);
   }
-  if (int rc = rdst_launch_status("lnlin_bwd")) return rc;
+  if (rc) return rc;
   return lnlin_bwd_reduce(slab, (int)grid, p.slab_stride, ln, Wt, ln_w, ln_b, dW, dbias, dln_w, dln_b, G, N, K, st);
 }

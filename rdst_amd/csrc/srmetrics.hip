@@ -203,10 +203,9 @@ extern "C" int rdst_sr_scores(const float* gt, const float* pred, int N, int C, 
   const double C1 = (0.01 * data_range) * (0.01 * data_range), C2 = (0.03 * data_range) * (0.03 * data_range);
   const int smem = smem_bytes(win);
   hipStream_t st = (hipStream_t)stream;
-  (void)hipFuncSetAttribute((const void*)srm_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-  hipLaunchKernelGGL(srm_tile_kernel, dim3((unsigned)(N * tiles)), dim3(NT), smem, st, gt, pred, H, W, margin, win, ty, tx,
-                     C1, C2, (double*)workspace);
-  if (int rc = rdst_launch_status(who)) return rc;
+  if (int rc = rdst_launch(srm_tile_kernel, dim3((unsigned)(N * tiles)), dim3(NT), smem, st, who, gt, pred, H, W, margin, win, ty, tx,
+                           C1, C2, (double*)workspace))
+    return rc;
   hipLaunchKernelGGL(srm_finish_kernel, dim3((unsigned)N), dim3(64), 0, st, (const double*)workspace, (int)tiles,
                      (double)C * Hc * Wc, (double)C * (Hc - 2 * p) * (Wc - 2 * p), mse, ssim);
   return rdst_launch_status(who);

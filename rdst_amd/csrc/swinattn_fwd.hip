@@ -26,6 +26,7 @@
 // SIMD cycles each) issued by three waves per SIMD that reach the same dependency at the same time — not bytes (0.33-0.41
 // of 8 TB/s), not the matrix pipe (16 % busy).  Seven variants of the store / copy / prefetch structure were measured on one
 // box each (tools/sa_ab.sh); the switches below keep the ones that are still a compile-time choice.
+#include "lds_dma.h"
 #include "wattn_hd.h"
 #include "pack.h"
 #include "linear.h"
@@ -73,7 +74,7 @@ struct SA {
   static constexpr int HEADS = 6, C = HEADS * D;
   static constexpr int KS = (C + 15) / 16, NTS = (C + 31) / 32, NTQ = 3 * NTS;   // 4/6/8 k-steps, 2/3/4 tiles per section
   // x tile: [64 tokens][XS bytes], odd number of 16-byte slots (b128 row reads), XD slots carry data
-  static constexpr int XS0 = KS * 32, XS = ((XS0 / 16) & 1) ? XS0 : XS0 + 16, XSLOTS = XS / 16, XD = (2 * C + 15) / 16;
+  static constexpr int XS = lds_kstep_stride(C), XSLOTS = XS / 16, XD = (2 * C + 15) / 16;
   static constexpr int XBUFB = 64 * XS;
   static constexpr int WSLOTS = 16 * XSLOTS, WPIECES = (WSLOTS + 63) / 64;       // a loader wave's 16 rows: slots, DMA pieces
   // Q / K sections and the O tile: row stride XS (b128 row reads only); V: K1's row stride (transposed reads: a 256-byte row
@@ -231,22 +232,8 @@ __global__ void __launch_bounds__(64 * sa_nw(D), 3) swinattn_fwd_kernel(const SA
   const float* sbpL = reinterpret_cast<const float*>(smem + CF::OFF_SBP);
   float* statL = reinterpret_cast<float*>(smem + CF::OFF_ST);
 
-  typedef uint32_t u32x4s_t __attribute__((ext_vector_type(4)));
-  auto make_rsrc = [&](const void* ptr, uint32_t bytes) {
-    u32x4s_t q;
-    q.x = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)ptr);
-    q.y = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)ptr >> 32) & 0xffffu);
-    q.z = __builtin_amdgcn_readfirstlane(bytes);
-    q.w = 0x00020000u;
-    return q;
-  };
-  const u32x4s_t rsx = make_rsrc(p.X, p.x_bytes);
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  auto dma = [&](const u32x4s_t& rs, uint32_t ldst, uint32_t off) {   // inline asm: see conv3_mfma.hip
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(off), "s"(ldst), "s"(rs) : "memory");
-  };
+  const u32x4s_t rsx = dma_rsrc(p.X, p.x_bytes);
+  const uint32_t lds0 = lds_base(smem);
 
   // ---- G1 work of this wave: tile tq, token halves [hf0, hf1) ---------------------------------------------------------
   //   D = 20: 12 tiles, wave = tile, both halves;  D = 10: 6 tiles x 2 halves = one item per wave;
@@ -262,12 +249,11 @@ __global__ void __launch_bounds__(64 * sa_nw(D), 3) swinattn_fwd_kernel(const SA
     else { tq = 6 + (wv - 6) % 3; hf0 = (wv - 6) / 3; hf1 = hf0 + 1; }
   }
   // its weight fragments, loaded by inline asm before anything else is in flight (lin3_mfma.hip)
-  typedef uint32_t u32x4v_t __attribute__((ext_vector_type(4)));
   u32x4v_t wfr[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
     const char* src = reinterpret_cast<const char*>(p.Wq) + (((int64_t)tq * KS + ks) * 64 + lane) * 16;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(wfr[ks]) : "v"(src) : "memory");
+    frag_load(wfr[ks], src);
   }
   const int secq = tq / NTS, chq = (tq - secq * NTS) * 32;   // section and first channel of the tile
 
@@ -299,7 +285,7 @@ __global__ void __launch_bounds__(64 * sa_nw(D), 3) swinattn_fwd_kernel(const SA
       const uint32_t t = (uint32_t)token(w, (16 * wv + rl) & 63);
       const uint32_t off = sl < CF::XD ? t * ldxb + (uint32_t)(sl * 16) : 0xffffffffu;
       if (s < CF::WSLOTS)
-        dma(rsx, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::OFF_X + buf * CF::XBUFB + 16 * wv * XS + i * 1024)), off);
+        lds_dma16(rsx, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(CF::OFF_X + buf * CF::XBUFB + 16 * wv * XS + i * 1024)), off);
     }
   };
   // LayerNorm statistics of the loader wave's own 16 rows (4 lanes per token, two passes: lin3_mfma.hip) -> LDS + HBM
@@ -403,9 +389,9 @@ __global__ void __launch_bounds__(64 * sa_nw(D), 3) swinattn_fwd_kernel(const SA
   c.scale2 = p.scale * LOG2E;
 
   // every load of the prologue has landed (weights, table, proj image, the loader waves' rows of window 0)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
 #pragma unroll
-  for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(wfr[ks]));
+  for (int ks = 0; ks < KS; ++ks) frag_pin(wfr[ks]);
   if (loader && win < nwin) row_stats(cur, 0, lane);
 
   // whole-row copies LDS -> HBM: instruction i of a tile moves chunks 64 i .. 64 i + 63 of its 64 x CPR chunks; the waves
@@ -449,15 +435,15 @@ __global__ void __launch_bounds__(64 * sa_nw(D), 3) swinattn_fwd_kernel(const SA
   bool have_prev = false;
   WinPos prev = cur;
 #ifdef SA_STAMPS
-  unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl = __builtin_readcyclecounter(), tn;
-#define SA_ST(k) { tn = __builtin_readcyclecounter(); tacc[k] += tn - tl; tl = tn; }
+#define SA_ON 1
 #else
-#define SA_ST(k)
+#define SA_ON 0
 #endif
-  SA_ST(0)   // 0: prologue
+  RDST_PHASES_BEGIN(SA_ON);
+  RDST_PHASE(SA_ON, 0)   // 0: prologue
   for (; win < nwin; win += p.G) {
     __syncthreads();   // top: x(n) + statistics in LDS; everybody is done with window n - 1
-    SA_ST(1)   // 1: wait at the top barrier
+    RDST_PHASE(SA_ON, 1)   // 1: wait at the top barrier
     const WinPos w = cur;
     const int nxt = win + p.G;
     const bool more = nxt < nwin;
@@ -539,9 +525,9 @@ __global__ void __launch_bounds__(64 * sa_nw(D), 3) swinattn_fwd_kernel(const SA
     // the previous window's x1 rows (written in place of its x tile, phase C) and a rows (the O tile) -> HBM
     if (have_prev && !(SA_ABL & 4)) copy_rows(smem + CF::OFF_X + (buf ^ 1) * CF::XBUFB, XS, p.x1, p.ld1, prev, lnw, 0, SA_NW);
     if (!SA_ACOPY_C && have_prev && !(SA_ABL & 2)) copy_rows(Os, ldq, p.a, p.lda, prev, lnw, 0, SA_NW);
-    SA_ST(2)   // 2: phase A work
+    RDST_PHASE(SA_ON, 2)   // 2: phase A work
     __syncthreads();   // B1: the window's q | k | v are in LDS; the other x buffer is free
-    SA_ST(3)   // 3: wait at B1
+    RDST_PHASE(SA_ON, 3)   // 3: wait at B1
 
     // ---- B: next rows in flight, qkv rows out, attention -------------------------------------------------------------------
     if (loader && more && !(SA_ABL & 64)) issue(cur, buf ^ 1, lnw);
@@ -576,14 +562,14 @@ __global__ void __launch_bounds__(64 * sa_nw(D), 3) swinattn_fwd_kernel(const SA
         }
       }
     }
-    SA_ST(4)   // 4: phase B work
+    RDST_PHASE(SA_ON, 4)   // 4: phase B work
     __syncthreads();   // B2: the attention output a is in the O tile
-    SA_ST(5)   // 5: wait at B2
+    RDST_PHASE(SA_ON, 5)   // 5: wait at B2
 
     // ---- C: a rows out, proj + shortcut (x1 in place of x); the loader waves: statistics of the next window ------------
     if (loader) {
       // the next window's rows of this wave have landed (issued an attention phase ago)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
       if (more) row_stats(cur, buf ^ 1, lnw);
       if (SA_ACOPY_C && !(SA_ABL & 2)) copy_rows(Os, ldq, p.a, p.lda, w, lnw, 0, SA_NLW);
     }
@@ -643,14 +629,11 @@ __global__ void __launch_bounds__(64 * sa_nw(D), 3) swinattn_fwd_kernel(const SA
     prev = w;
     have_prev = true;
     buf ^= 1;
-    SA_ST(6)   // 6: phase C work
+    RDST_PHASE(SA_ON, 6)   // 6: phase C work
   }
   __syncthreads();
 #ifdef SA_STAMPS
-  if (p.stamps && lane == 0) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) p.stamps[((size_t)blockIdx.x * SA_NW + wv) * 8 + k] = tacc[k];
-  }
+  RDST_PHASES_STORE(p.stamps && lane == 0, p.stamps, (size_t)blockIdx.x * SA_NW + wv);
 #endif
   if (have_prev && !(SA_ABL & 4)) {   // the last window's x1 rows
     int lnw = tid;
@@ -668,8 +651,6 @@ int launch_sa(SAArgs& p, hipStream_t st) {
   constexpr int WGCU = SA_NW == 6 ? 2 : 1;   // workgroups per CU
   static_assert(WGCU * CF::SMEM <= 160 * 1024, "LDS per CU");
   auto kern = swinattn_fwd_kernel<D>;
-  // (per launch: the attribute is per DEVICE, a process-wide "done" flag would leave a second GPU without it)
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
   const int64_t nwin = (int64_t)p.g.B * p.g.nWh * p.g.nWw;
   int64_t G = 256 * WGCU;
   if (G > nwin) G = nwin;
@@ -682,7 +663,7 @@ int launch_sa(SAArgs& p, hipStream_t st) {
       const size_t n = (size_t)G * SA_NW * 8;
       (void)hipMalloc((void**)&p.stamps, n * 8);
       (void)hipMemsetAsync(p.stamps, 0, n * 8, st);
-      hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(SA_NTH), CF::SMEM, st, p);
+      const int rc = rdst_launch(kern, dim3((unsigned)G), dim3(SA_NTH), CF::SMEM, st, "swinattn_fwd", p);
       (void)hipStreamSynchronize(st);
       unsigned long long* hst = (unsigned long long*)malloc(n * 8);
       (void)hipMemcpy(hst, p.stamps, n * 8, hipMemcpyDeviceToHost);
@@ -701,13 +682,12 @@ int launch_sa(SAArgs& p, hipStream_t st) {
         }
       }
       free(hst);
-      return rdst_launch_status("swinattn_fwd");
+      return rc;
     }
     p.stamps = nullptr;
   }
 #endif
-  hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(SA_NTH), CF::SMEM, st, p);
-  return rdst_launch_status("swinattn_fwd");
+  return rdst_launch(kern, dim3((unsigned)G), dim3(SA_NTH), CF::SMEM, st, "swinattn_fwd", p);
 }
 
 }  // namespace

@@ -533,10 +533,8 @@ int launch_f16_fwd(const F16Args& p, hipStream_t st) {
   auto kern = wattn16_f32_fwd_kernel<D>;
   constexpr size_t smem = F16<D>::SMEM_FWD;
   static_assert(smem <= 160 * 1024, "LDS");
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   const int64_t nwin = (int64_t)p.g.B * p.g.nWh * p.g.nWw;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(6 * nwin)), dim3(512), smem, st, p);
-  return rdst_launch_status("wattn16_f32_fwd");
+  return rdst_launch(kern, dim3((unsigned)(6 * nwin)), dim3(512), smem, st, "wattn16_f32_fwd", p);
 }
 
 template <int D>
@@ -544,10 +542,8 @@ int launch_f16_bwd(const F16Args& p, hipStream_t st) {
   auto kern = wattn16_f32_bwd_kernel<D>;
   constexpr size_t smem = F16<D>::SMEM_BWD;
   static_assert(smem <= 160 * 1024, "LDS");
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   const int64_t nwin = (int64_t)p.g.B * p.g.nWh * p.g.nWw;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(6 * nwin)), dim3(512), smem, st, p);
-  return rdst_launch_status("wattn16_f32_bwd");
+  return rdst_launch(kern, dim3((unsigned)(6 * nwin)), dim3(512), smem, st, "wattn16_f32_bwd", p);
 }
 
 bool al(const void* a, int64_t lda_bytes, int gsz) { return (uintptr_t)a % gsz == 0 && lda_bytes % gsz == 0; }

@@ -316,11 +316,8 @@ int launch_fwd16(const W16Args& p, hipStream_t st) {
   auto kern = wattn16_fwd_kernel<D>;
   constexpr size_t smem = w16_fwd_smem<D>();
   static_assert(smem <= 80 * 1024, "two workgroups per CU");
-  if (smem > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   const int64_t nwin = (int64_t)p.g.B * p.g.nWh * p.g.nWw;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(3 * nwin)), dim3(256), smem, st, p);
-  return rdst_launch_status("wattn16_fwd");
+  return rdst_launch(kern, dim3((unsigned)(3 * nwin)), dim3(256), smem, st, "wattn16_fwd", p);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1364,28 +1361,22 @@ int launch_bwd16(const W16Args& p, hipStream_t st) {
       auto k1 = wattn16_bwd1_kernel<D>;
       constexpr size_t smem1 = W16B1<D>::SMEM;
       static_assert(smem1 <= 80 * 1024, "two workgroups per CU");
-      (void)hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem1);
       const int64_t nwin1 = (int64_t)p.g.B * p.g.nWh * p.g.nWw;
-      hipLaunchKernelGGL(k1, dim3((unsigned)(6 * nwin1)), dim3(512), smem1, st, p);
-      return rdst_launch_status("wattn16_bwd1");
+      return rdst_launch(k1, dim3((unsigned)(6 * nwin1)), dim3(512), smem1, st, "wattn16_bwd1", p);
     }
   }
   if (W16_BWD3 && p.nlse && p.o) {
     auto k3 = wattn16_bwd3_kernel<D>;
     constexpr size_t smem3 = W16B3<D>::SMEM;
     static_assert(smem3 <= 160 * 1024, "LDS");
-    (void)hipFuncSetAttribute((const void*)k3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem3);
     const int64_t nwin3 = (int64_t)p.g.B * p.g.nWh * p.g.nWw;
-    hipLaunchKernelGGL(k3, dim3((unsigned)(3 * nwin3)), dim3(1024), smem3, st, p);
-    return rdst_launch_status("wattn16_bwd3");
+    return rdst_launch(k3, dim3((unsigned)(3 * nwin3)), dim3(1024), smem3, st, "wattn16_bwd3", p);
   }
   auto kern = (p.nlse && p.o) ? wattn16_bwd_kernel<D, true> : wattn16_bwd_kernel<D, false>;
   constexpr size_t smem = W16B<D>::SMEM;
   static_assert(smem <= 160 * 1024, "LDS");
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   const int64_t nwin = (int64_t)p.g.B * p.g.nWh * p.g.nWw;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(3 * nwin)), dim3(512), smem, st, p);
-  return rdst_launch_status("wattn16_bwd");
+  return rdst_launch(kern, dim3((unsigned)(3 * nwin)), dim3(512), smem, st, "wattn16_bwd", p);
 }
 
 bool al(const void* a, int64_t lda_bytes, int gsz) { return (uintptr_t)a % gsz == 0 && lda_bytes % gsz == 0; }

@@ -567,13 +567,13 @@ int launch_bwd(const T* qkv, int64_t ld, const float* table, const T* dout, int6
   const int per_row = 3 * sec / gran;
   const int iters = (per_row + 63) / 64;
   constexpr int NWV = sizeof(T) == 4 ? 8 : NUNITS;
+  int rc = 0;
 #define RDST_WB_LAUNCH(GR, IT, CT)                                                                                   \
   {                                                                                                                  \
     auto kern = wattn_bwd_mfma_kernel<T, GR, IT, NWV, CT>;                                                                 \
     if constexpr (sizeof(T) == 4)                                                                                    \
       if (split) kern = wattn_bwd_mfma_kernel<T, GR, IT, NWV, CT, true>;                                             \
-    if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * NWV), smem, st, p);                                        \
+    rc = rdst_launch(kern, dim3((unsigned)grid), dim3(64 * NWV), smem, st, "wattn_bwd_mfma", p);                      \
   }
   bool done = false;
   if constexpr (sizeof(T) == 4) {   // the fp32 parity mode's three widths, channel count at compile time
@@ -591,7 +591,7 @@ int launch_bwd(const T* qkv, int64_t ld, const float* table, const T* dout, int6
   else if (gran == 4 && iters <= 3) RDST_WB_LAUNCH(4, 3, 0)
   else return RDST_ENOTSUP;
 #undef RDST_WB_LAUNCH
-  return rdst_launch_status("wattn_bwd_mfma");
+  return rc;
 }
 
 }  // namespace

@@ -571,8 +571,6 @@ template <int D, int HEADS, int GRAN>
 int launch_bw(const BwArgs& p, int slab_rows, int* nslab, hipStream_t st) {
   using CF = HdB<D, HEADS>;
   auto kern = wattn_bwd_hd_kernel<D, HEADS, GRAN>;
-  if (CF::SMEM > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CF::SMEM);
   constexpr int NT2 = 128 * HEADS, NG = HEADS_ALL / HEADS;
   const int64_t nwin = (int64_t)p.g.B * p.g.nWh * p.g.nWw;
   int64_t G = 256;      // window groups: NG workgroups each, 256 x NG workgroups = 12 waves per CU
@@ -592,7 +590,7 @@ int launch_bw(const BwArgs& p, int slab_rows, int* nslab, hipStream_t st) {
     const size_t n = (size_t)grid * 16;
     (void)hipMalloc((void**)&q.stamps, n * 8);
     (void)hipMemsetAsync(q.stamps, 0, n * 8, st);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT2), CF::SMEM, st, q);
+    const int rc = rdst_launch(kern, dim3((unsigned)grid), dim3(NT2), CF::SMEM, st, "wattn_bwd_hd", q);
     (void)hipStreamSynchronize(st);
     unsigned long long* hst = (unsigned long long*)malloc(n * 8);
     (void)hipMemcpy(hst, q.stamps, n * 8, hipMemcpyDeviceToHost);
@@ -611,10 +609,9 @@ int launch_bw(const BwArgs& p, int slab_rows, int* nslab, hipStream_t st) {
         if (cnt[k]) fprintf(stderr, "  %2d: %9.0f\n", k, sum[k] / cnt[k]);
     }
     free(hst);
-    return rdst_launch_status("wattn_bwd_hd");
+    return rc;
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT2), CF::SMEM, st, pg);
-  return rdst_launch_status("wattn_bwd_hd");
+  return rdst_launch(kern, dim3((unsigned)grid), dim3(NT2), CF::SMEM, st, "wattn_bwd_hd", pg);
 }
 
 bool aligned_to(const void* a, const void* b, const void* cc, int64_t la, int64_t lb, int64_t lc, int gsz) {

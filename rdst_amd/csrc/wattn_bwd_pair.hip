@@ -23,6 +23,7 @@
 // does not end on a slot boundary drags the first channels of the next head pair along: finite values that the
 // compile-time channel masks of the Q / dO packs (T) and K / V packs (N) multiply by zero — which is why the rows must be
 // DENSE (ld = 3C / C): the bytes behind a piece are then activations, never uninitialised memory.
+#include "lds_dma.h"
 #include "wattn_hd.h"
 #include <stdlib.h>
 
@@ -334,22 +335,8 @@ __global__ void __launch_bounds__(NTH, 3) wattn_bwd_pair_kernel(const PArgs p) {
   const int nwin = g.B * nW;
 
   // ---- LDS-DMA plumbing (inline asm: the compiler must not see these loads, or it drains the queue at every LDS read) ----
-  typedef uint32_t u32x4s_t __attribute__((ext_vector_type(4)));
-  auto make_rsrc = [&](const void* ptr, uint32_t bytes) {
-    u32x4s_t q;
-    q.x = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)ptr);
-    q.y = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)ptr >> 32) & 0xffffu);
-    q.z = __builtin_amdgcn_readfirstlane(bytes);
-    q.w = 0x00020000u;
-    return q;
-  };
-  const u32x4s_t rs_qkv = make_rsrc(p.qkv, p.qkv_bytes), rs_do = make_rsrc(p.dout, p.dout_bytes);
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(LDS_AS char*)smem;
-  auto dma = [&](const u32x4s_t& rs, uint32_t ldst, uint32_t off) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(off), "s"(ldst), "s"(rs) : "memory");
-  };
+  const u32x4s_t rs_qkv = dma_rsrc(p.qkv, p.qkv_bytes), rs_do = dma_rsrc(p.dout, p.dout_bytes);
+  const uint32_t lds0 = lds_base(smem);
   struct WinPos { int b, wr, wc; };
   auto locate = [&](int win) {
     WinPos w;
@@ -396,7 +383,7 @@ __global__ void __launch_bounds__(NTH, 3) wattn_bwd_pair_kernel(const PArgs p) {
         const uint32_t t = (uint32_t)(rb + colv[pl & 1]);
         const uint32_t off = data ? t * (is_do ? lddb : ldb) + (uint32_t)((is_do ? 0 : sec * CF::CFULL) * 2) + sloff : 0xffffffffu;
         if (on)
-          dma(is_do ? rs_do : rs_qkv, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(buf * CF::BUFB + sec * CF::SECB + pl * 4 * ldt)), off);
+          lds_dma16(is_do ? rs_do : rs_qkv, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(buf * CF::BUFB + sec * CF::SECB + pl * 4 * ldt)), off);
       }
       return;
     }
@@ -409,7 +396,7 @@ __global__ void __launch_bounds__(NTH, 3) wattn_bwd_pair_kernel(const PArgs p) {
       const uint32_t t = (uint32_t)token(w, row & 63);
       const uint32_t off = sl < SD ? t * (is_do ? lddb : ldb) + (uint32_t)(((is_do ? 0 : sec * CF::CFULL) + ch0) * 2 + sl * 16) : 0xffffffffu;
       if (rl < CF::RPP && row < 64)
-        dma(is_do ? rs_do : rs_qkv, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(buf * CF::BUFB + sec * CF::SECB + pl * CF::RPP * ldt)), off);
+        lds_dma16(is_do ? rs_do : rs_qkv, __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(buf * CF::BUFB + sec * CF::SECB + pl * CF::RPP * ldt)), off);
     }
   };
 
@@ -496,8 +483,8 @@ __global__ void __launch_bounds__(NTH, 3) wattn_bwd_pair_kernel(const PArgs p) {
     for (int v = 0; v < 16; ++v) Dsum[kt][v] = 0.f;
 
   // every wave: the table loads are done; loader waves: item 0 has landed, items 1 .. NBUF - 2 stay in flight
-  if (NBUF > 2 && loader) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CF::PPW * (NBUF - 2)) : "memory");
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (NBUF > 2 && loader) wait_vmcnt<CF::PPW * (NBUF - 2)>();
+  else wait_vmcnt<0>();
   int buf = 0;
   for (; win < nwin; win += p.G) {
     __syncthreads();  // b0: this item's rows have landed (the loader waves waited for them); the buffer of the previous item is free
@@ -622,8 +609,8 @@ __global__ void __launch_bounds__(NTH, 3) wattn_bwd_pair_kernel(const PArgs p) {
     } else {
       // the loader waves: the next item's rows have landed; the NBUF - 2 younger items stay in flight.  These waves have
       // no store outstanding (completion is reported in issue order: a load behind a store would wait for the store)
-      if (NBUF > 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CF::PPW * (NBUF - 2)) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (NBUF > 2) wait_vmcnt<CF::PPW * (NBUF - 2)>();
+      else wait_vmcnt<0>();
     }
     buf = buf == NBUF - 1 ? 0 : buf + 1;
   }
@@ -677,9 +664,7 @@ int launch_pair(const PArgs& p0, int slab_rows, int* nslab, hipStream_t st) {
   *nslab = (int)G;
   PArgs p = p0;
   p.G = (int)G;
-  if (CF::SMEM > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CF::SMEM);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(G * NG)), dim3(NTH), CF::SMEM, st, p);
-  return rdst_launch_status("wattn_bwd_pair");
+  return rdst_launch(kern, dim3((unsigned)(G * NG)), dim3(NTH), CF::SMEM, st, "wattn_bwd_pair", p);
 }
 
 }  // namespace

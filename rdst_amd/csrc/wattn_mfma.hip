@@ -394,13 +394,13 @@ int launch_fwd(const T* qkv, int64_t ld, const float* table, T* out, int64_t ldo
   if (wg_per_cu < 1) wg_per_cu = 1;
   int64_t grid = 256 * wg_per_cu;
   if (grid > nwin) grid = nwin;
+  int rc = 0;
 #define RDST_WA_LAUNCH1(GR, KM, NWV)                                                                                  \
   {                                                                                                                  \
     auto kern = wattn_fwd_mfma_kernel<T, GR, KM, NWV>;                                                               \
     if constexpr (sizeof(T) == 4)                                                                                    \
       if (split) kern = wattn_fwd_mfma_kernel<T, GR, KM, NWV, true>;                                                 \
-    if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * NWV), smem, st, p);                                     \
+    rc = rdst_launch(kern, dim3((unsigned)grid), dim3(64 * NWV), smem, st, "wattn_fwd_mfma", p);                      \
   }
 #define RDST_WA_LAUNCH(GR, KM)                                                                                        \
   {                                                                                                                  \
@@ -414,7 +414,7 @@ int launch_fwd(const T* qkv, int64_t ld, const float* table, T* out, int64_t ldo
   else return RDST_ENOTSUP;
 #undef RDST_WA_LAUNCH
 #undef RDST_WA_LAUNCH1
-  return rdst_launch_status("wattn_fwd_mfma");
+  return rc;
 }
 
 }  // namespace

@@ -415,8 +415,6 @@ template <int D, int HEADS, int GRAN, int ITERS, int MINB>
 int launch_hd(const HdArgs& p, hipStream_t st) {
   using CF = Hd<D, HEADS>;
   auto kern = wattn_fwd_hd_kernel<D, HEADS, GRAN, ITERS, MINB>;
-  if (CF::SMEM > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CF::SMEM);
   const int64_t nwin = (int64_t)p.g.B * p.g.nWh * p.g.nWw;
   int wg_per_cu = (int)((160 * 1024) / CF::SMEM);
   if (wg_per_cu > MINB) wg_per_cu = MINB;
@@ -440,7 +438,7 @@ int launch_hd(const HdArgs& p, hipStream_t st) {
     const size_t n = (size_t)grid * 16;
     (void)hipMalloc((void**)&q.stamps, n * 8);
     (void)hipMemsetAsync(q.stamps, 0, n * 8, st);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), CF::SMEM, st, q);
+    const int rc = rdst_launch(kern, dim3((unsigned)grid), dim3(256), CF::SMEM, st, "wattn_fwd_hd", q);
     (void)hipStreamSynchronize(st);
     unsigned long long* hst = (unsigned long long*)malloc(n * 8);
     (void)hipMemcpy(hst, q.stamps, n * 8, hipMemcpyDeviceToHost);
@@ -465,10 +463,9 @@ int launch_hd(const HdArgs& p, hipStream_t st) {
         if (cnt[k]) fprintf(stderr, "  %2d: %5d %9.0f %9.0f %9.0f\n", k, cnt[k], sum[k] / cnt[k], mn[k], mx[k]);
     }
     free(hst);
-    return rdst_launch_status("wattn_fwd_hd");
+    return rc;
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), CF::SMEM, st, p);
-  return rdst_launch_status("wattn_fwd_hd");
+  return rdst_launch(kern, dim3((unsigned)grid), dim3(256), CF::SMEM, st, "wattn_fwd_hd", p);
 }
 
 bool aligned_to(const void* a, const void* b, int64_t lda_bytes, int64_t ldb_bytes, int gsz) {

@@ -252,11 +252,11 @@ int launch_fwd_d(int D, const T* qkv, int64_t ld, const float* table, T* out, in
   const int bd = N >= 256 ? 256 : ((N + 63) / 64) * 64;
   const dim3 grid((unsigned)((int64_t)g.B * g.nWh * g.nWw * g.heads));
   if (smem > 160 * 1024) return rdst_fail(RDST_ENOTSUP, "rdst_wattn_fwd: window %d x head dim %d exceeds LDS", g.ws, D);
+  int rc = 0;
 #define RDST_FWD_CASE(DD)                                                                        \
   case DD: {                                                                                     \
     auto kern = wattn_fwd_v0<T, DD>;                                                             \
-    if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-    hipLaunchKernelGGL(kern, grid, dim3(bd), smem, st, qkv, ld, table, out, ldo, g, scale);      \
+    rc = rdst_launch(kern, grid, dim3(bd), smem, st, "wattn_fwd_v0", qkv, ld, table, out, ldo, g, scale);             \
   } break;
   switch (D) {
     RDST_FWD_CASE(4) RDST_FWD_CASE(5) RDST_FWD_CASE(8) RDST_FWD_CASE(10) RDST_FWD_CASE(12) RDST_FWD_CASE(15)
@@ -265,7 +265,7 @@ int launch_fwd_d(int D, const T* qkv, int64_t ld, const float* table, T* out, in
       return rdst_fail(RDST_ENOTSUP, "rdst_wattn_fwd: head dim %d not supported by the generic kernel", D);
   }
 #undef RDST_FWD_CASE
-  return rdst_launch_status("wattn_fwd_v0");
+  return rc;
 }
 
 template <typename T>
@@ -276,11 +276,11 @@ int launch_bwd_d(int D, const T* qkv, int64_t ld, const float* table, const T* d
   if (smem > 160 * 1024) return rdst_fail(RDST_ENOTSUP, "rdst_wattn_bwd: window %d x head dim %d exceeds LDS", g.ws, D);
   const int bd = N >= 256 ? 256 : ((N + 63) / 64) * 64;
   const dim3 grid((unsigned)((int64_t)g.B * g.nWh * g.nWw * g.heads));
+  int rc = 0;
 #define RDST_BWD_CASE(DD)                                                                         \
   case DD: {                                                                                      \
     auto kern = wattn_bwd_v0<T, DD>;                                                              \
-    if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-    hipLaunchKernelGGL(kern, grid, dim3(bd), smem, st, qkv, ld, table, dout, ldd, dqkv, ldq, slab, g, scale); \
+    rc = rdst_launch(kern, grid, dim3(bd), smem, st, "wattn_bwd_v0", qkv, ld, table, dout, ldd, dqkv, ldq, slab, g, scale); \
   } break;
   switch (D) {
     RDST_BWD_CASE(4) RDST_BWD_CASE(5) RDST_BWD_CASE(8) RDST_BWD_CASE(10) RDST_BWD_CASE(12) RDST_BWD_CASE(15)
@@ -289,7 +289,7 @@ int launch_bwd_d(int D, const T* qkv, int64_t ld, const float* table, const T* d
       return rdst_fail(RDST_ENOTSUP, "rdst_wattn_bwd: head dim %d not supported by the generic kernel", D);
   }
 #undef RDST_BWD_CASE
-  return rdst_launch_status("wattn_bwd_v0");
+  return rc;
 }
 
 }  // namespace

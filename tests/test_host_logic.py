@@ -393,3 +393,13 @@ def test_reduce_batch_bookkeeping_nesting_foreign_pass_and_reset(monkeypatch):
     assert calls[:2] == ["rdst_reduce_batch_abort", "rdst_reduce_batch_begin"] and RB.depth == 1
     RB.end(lib)
     assert RB.depth == 0
+
+
+def test_lds_dma_idiom_lives_in_one_header():
+    # the LDS-DMA issue and the buffer descriptor's format word are written once, in lds_dma.h: a kernel that pastes either
+    # again shows up here
+    csrc = os.path.join(ROOT, "rdst_amd", "csrc")
+    for needle in ("offen lds", "0x00020000u"):
+        holders = sorted(f for f in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, f))
+                         and needle in open(os.path.join(csrc, f), errors="replace").read())
+        assert holders == ["lds_dma.h"], (needle, holders)

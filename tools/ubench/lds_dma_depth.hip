@@ -8,22 +8,16 @@
 //   total  = cycles until vmcnt(0), per instruction            (1 KB / total = bytes per cycle and wave)
 // beside the same bytes as global_load_dwordx4 into registers (16 in flight per wave) + ds_write_b128.
 // build: hipcc --offload-arch=gfx950 -O3 -w tools/ubench/lds_dma_depth.hip -o tools/ubench/lds_dma_depth.bin
-#include <hip/hip_runtime.h>
+#include "../../rdst_amd/csrc/lds_dma.h"   // the kernels' own descriptor / LDS-DMA / fragment-load helpers
 #include <cstdio>
 #include <cstdlib>
-typedef uint32_t u32x4s_t __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 template <int N>
 __global__ void __launch_bounds__(1024) dma_kernel(const char* src, long long bytes, long long* out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), nw = blockDim.x >> 6;
-  u32x4s_t rs;
-  rs.x = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)src);
-  rs.y = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)src >> 32) & 0xffffu);
-  rs.z = __builtin_amdgcn_readfirstlane((uint32_t)bytes);
-  rs.w = 0x00020000u;
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+  const u32x4s_t rs = dma_rsrc(src, (uint32_t)bytes);
+  const uint32_t lds0 = lds_base(smem);
   // piece p of this wave: 1 KB at a cold place of the buffer (workgroup, wave and piece spread far apart)
   const uint32_t base = (uint32_t)((((long long)blockIdx.x * nw + wave) * N) * 1024 % (bytes - 1024 * 64)) + lane * 16;
   __syncthreads();
@@ -31,12 +25,10 @@ __global__ void __launch_bounds__(1024) dma_kernel(const char* src, long long by
 #pragma unroll
   for (int i = 0; i < N; ++i) {
     const uint32_t dst = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)((wave * 4 + (i & 3)) * 1024));
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(base + i * 1024), "s"(dst), "s"(rs) : "memory");
+    lds_dma16(rs, dst, base + i * 1024);
   }
   const long long t1 = __builtin_amdgcn_s_memtime();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
   const long long t2 = __builtin_amdgcn_s_memtime();
   if (lane == 0) { out[(blockIdx.x * nw + wave) * 2] = t1 - t0; out[(blockIdx.x * nw + wave) * 2 + 1] = t2 - t0; }
 }
@@ -46,17 +38,17 @@ __global__ void __launch_bounds__(1024) reg_kernel(const char* src, long long by
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), nw = blockDim.x >> 6;
   const char* p = src + ((((long long)blockIdx.x * nw + wave) * N) * 1024 % (bytes - 1024 * 64)) + lane * 16;
-  u32x4 v[N];
+  u32x4v_t v[N];
   __syncthreads();
   const long long t0 = __builtin_amdgcn_s_memtime();
 #pragma unroll
-  for (int i = 0; i < N; ++i) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v[i]) : "v"(p + i * 1024) : "memory");
+  for (int i = 0; i < N; ++i) frag_load(v[i], p + i * 1024);
   const long long t1 = __builtin_amdgcn_s_memtime();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
 #pragma unroll
   for (int i = 0; i < N; ++i) {
-    asm volatile("" : "+v"(v[i]));
-    *reinterpret_cast<u32x4*>(smem + (wave * 4 + (i & 3)) * 1024 + lane * 16) = v[i];
+    frag_pin(v[i]);
+    *reinterpret_cast<u32x4v_t*>(smem + (wave * 4 + (i & 3)) * 1024 + lane * 16) = v[i];
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   const long long t2 = __builtin_amdgcn_s_memtime();
