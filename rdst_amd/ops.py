@@ -184,45 +184,25 @@ class PackPlan:
         self.owner_sig = None
 
     @staticmethod
-    def _key(kind, w, lw, lb, b, N, K, s):
-        return (kind, w.data_ptr(), _ptr(lw) or 0, _ptr(lb) or 0, _ptr(b) or 0, N, K, float(s))
+    def _key(images):
+        """What a workspace holds: per image its kind, the addresses of (w, lw, lb, b), N, K and the scale.  A group (the two
+        images of K7 or K8) and the single images of the same weights (the composed path) are different entries."""
+        return tuple((kind, w.data_ptr(), _ptr(lw) or 0, _ptr(lb) or 0, _ptr(b) or 0, N, K, float(s))
+                     for kind, w, lw, lb, b, N, K, s, _ in images)
 
-    def record(self, kind, w, lw, lb, b, N, K, s, nbytes, key=None):
-        k = key if key is not None else self._key(kind, w, lw, lb, b, N, K, s)
-        if k not in self.keys:
-            self.keys[k] = len(self.specs)
+    def record(self, images):
+        """images: (kind, w, lw, lb, b, N, K, s, bytes) of every image of one op's workspace, in its layout.  They take
+        consecutive arena space: all but the last at their exact size (the kernel finds the next image right behind), the
+        last rounded up so that the next entry starts on a 256-byte boundary."""
+        k = self._key(images)
+        if k in self.keys:
+            return
+        self.keys[k] = len(self.specs)
+        for i, (kind, w, lw, lb, b, N, K, s, nbytes) in enumerate(images):
+            if i == len(images) - 1:
+                nbytes = (int(nbytes) + 255) // 256 * 256
             self.specs.append((kind, N, K, float(s), int(nbytes)))
             self.tensors.append((w, lw, lb, b))
-
-    def record_mlp(self, w1, lw, lb, b1, w2, b2, C, hid, nb1, nb2):
-        """Two consecutive Linear images (fc1 with the LayerNorm folded in, fc2) = the workspace layout of rdst_mlp_fwd."""
-        k = ("mlp", w1.data_ptr(), w2.data_ptr(), _ptr(lw) or 0, _ptr(lb) or 0, _ptr(b1) or 0, _ptr(b2) or 0)
-        if k not in self.keys:
-            self.record(PACK_LINEAR, w1, lw, lb, b1, hid, C, 1.0, nb1, key=k)
-            self.record(PACK_LINEAR, w2, None, None, b2, C, hid, 1.0, (nb2 + 255) // 256 * 256, key=k + ("fc2",))
-
-    def lookup_mlp(self, w1, lw, lb, b1, w2, b2):
-        k = ("mlp", w1.data_ptr(), w2.data_ptr(), _ptr(lw) or 0, _ptr(lb) or 0, _ptr(b1) or 0, _ptr(b2) or 0)
-        i = self.keys.get(k)
-        if i is None:
-            self.misses += 1
-            return None
-        return self.arena.data_ptr() + self.offsets[i]
-
-    def record_swinattn(self, wq, lw, lb, bq, wp, bp, C, nbq, nbp):
-        """The workspace layout of rdst_swin_attn_fwd: the sectioned qkv image (norm1 folded in), then the proj image."""
-        k = ("swinattn", wq.data_ptr(), wp.data_ptr(), _ptr(lw) or 0, _ptr(lb) or 0, _ptr(bq) or 0, _ptr(bp) or 0)
-        if k not in self.keys:
-            self.record(PACK_LINEAR_SEC3, wq, lw, lb, bq, 3 * C, C, 1.0, nbq, key=k)
-            self.record(PACK_LINEAR, wp, None, None, bp, C, C, 1.0, (nbp + 255) // 256 * 256, key=k + ("proj",))
-
-    def lookup_swinattn(self, wq, lw, lb, bq, wp, bp):
-        k = ("swinattn", wq.data_ptr(), wp.data_ptr(), _ptr(lw) or 0, _ptr(lb) or 0, _ptr(bq) or 0, _ptr(bp) or 0)
-        i = self.keys.get(k)
-        if i is None:
-            self.misses += 1
-            return None
-        return self.arena.data_ptr() + self.offsets[i]
 
     @staticmethod
     def signature(owner):
@@ -257,8 +237,9 @@ class PackPlan:
         _lib.check(_lib.load().rdst_pack_batch(ctypes.cast(self.jobs, ctypes.c_void_p), len(self.specs), _stream()),
                    "rdst_pack_batch")
 
-    def lookup(self, kind, w, lw, lb, b, N, K, s):
-        i = self.keys.get(self._key(kind, w, lw, lb, b, N, K, s))
+    def lookup(self, images):
+        """Address of the first image of that workspace in the arena, or None (counted in ``misses``)."""
+        i = self.keys.get(self._key(images))
         if i is None:
             self.misses += 1
             return None
@@ -348,36 +329,25 @@ class pack_scope:
         return False
 
 
-def _packed_workspace(kind, w, lw, lb, b, N, K, s, nbytes, device):
-    """(workspace pointer holder, pointer, workspace_bytes) for an op that reads a packed image of (w, lw, lb, b)."""
+def _packed_workspace(images, nbytes, device):
+    """(workspace holder, pointer, workspace_bytes) for an op that reads packed weight images: ``images`` lists
+    (kind, w, lw, lb, b, N, K, s, bytes) of each image in the op's ``nbytes`` workspace (Linear and conv: one; K7: fc1 +
+    fc2; K8: sectioned qkv + proj).  The protocol every such op follows: an active plan is asked for them, a recording
+    plan is told about them, and without a hit the op gets a private workspace and packs for itself."""
     if _plan_active is not None:
-        p = _plan_active.lookup(kind, w, lw, lb, b, N, K, s)
+        p = _plan_active.lookup(images)
         if p is not None:
             return None, p, _lib.PREPACKED
     if _plan_recording is not None:
-        _plan_recording.record(kind, w, lw, lb, b, N, K, s, (int(nbytes) + 255) // 256 * 256)
+        _plan_recording.record(images)
     wsp = _workspace(nbytes, device)
     return wsp, wsp.data_ptr(), int(nbytes)
 
 
-# The weight-gradient branch and the data-gradient branch of a Linear / conv backward are independent
-# and each under-fills the chip, so they run concurrently: wgrad on a side HIP stream, dgrad on the
-# current one, joined before the op returns (fork/join is capturable into a HIP graph).
-_side_streams: dict = {}
-TWO_STREAM_BACKWARD = os.environ.get("RDST_TWO_STREAM", "0") != "0"   # env switch: profiling with clean kernel durations
 MLP_FUSED = os.environ.get("RDST_MLP_FUSED", "1") != "0"   # K7 (fused Mlp kernels) on/off
 ATTN_LSE = os.environ.get("RDST_ATTN_LSE", "1") != "0"       # window 16: keep the forward's row statistics for the backward (rdst_wattn_*_lse)
 X3_STREAM = os.environ.get("RDST_X3_STREAM", "1") != "0"     # fp32x3: the streaming Linear kernels on prepacked hi / lo images (lin3x_mfma.hip, lnlin3x_mfma.hip) on/off
 ATTN_FUSED = os.environ.get("RDST_ATTN_FUSED", "1") != "0"   # K8 (LayerNorm + qkv -> attention -> proj + shortcut in one launch) on/off
-
-
-def _side_stream(device) -> "torch.cuda.Stream":
-    key = (device.index if device.index is not None else torch.cuda.current_device())
-    st = _side_streams.get(key)
-    if st is None:
-        st = torch.cuda.Stream(device=device)
-        _side_streams[key] = st
-    return st
 
 
 # ------------------------------------------------------------------------------------------------
@@ -458,47 +428,46 @@ def window_attention(qkv: torch.Tensor, table: torch.Tensor, H: int, W: int, hea
 
 
 def _linear_bwd_call(lib, x, ldx, lw, lb, stats, in_act, w, dy, lddy, dx, lddx, dx_add, ld_add, dw, db, dlw, dlb,
-                     M, K, N, out_scale, code, dev, join=True, keep=None, dx_add2=None, ld_add2=0):
-    """rdst_ln_linear_bwd with the weight-gradient half on the side stream (see TWO_STREAM_BACKWARD).
-    join=False leaves the side stream un-joined (the caller joins once, later) and parks the workspace in
-    `keep` so it outlives the asynchronous kernel.  dx_add2: a second (strided) addend of dx — folded into the
-    kernel where it takes one (rdst_ln_linear_bwd2), added afterwards otherwise."""
+                     M, K, N, out_scale, code, dev, keep=None, dx_add2=None, ld_add2=0):
+    """rdst_ln_linear_bwd: every gradient that is wanted (not None) in one call; nothing wanted, nothing launched.
+    `keep` (an open reduction batch's list) parks the workspace, whose slabs are read when the batch ends.
+    dx_add2: a second (strided) addend of dx — folded into the kernel where it takes one (rdst_ln_linear_bwd2),
+    added afterwards otherwise."""
+    if all(t is None for t in (dx, dlw, dlb, dw, db)):
+        return
     nbytes = lib.rdst_ln_linear_bwd_workspace(M, K, N)
+    wsp = _workspace(nbytes, dev)
+    if keep is not None:
+        keep.append(wsp)
+    args = (x.data_ptr(), ldx, _ptr(lw), _ptr(lb), _ptr(stats), in_act, _ptr(w), dy.data_ptr(), lddy, _ptr(dx), lddx,
+            _ptr(dx_add), ld_add, _ptr(dw), _ptr(db), _ptr(dlw), _ptr(dlb), wsp.data_ptr(), nbytes, M, K, N, out_scale, code,
+            _stream())
+    if dx_add2 is not None and dx is not None:
+        rc = lib.rdst_ln_linear_bwd2(*args, dx_add2.data_ptr(), ld_add2)
+        if rc != _lib.ENOTSUP:
+            _lib.check(rc, "rdst_ln_linear_bwd2")
+            return
+    _lib.check(lib.rdst_ln_linear_bwd(*args), "rdst_ln_linear_bwd")
+    if dx_add2 is not None and dx is not None:
+        dx.add_(dx_add2)
 
-    def call(dx_, add_, dw_, db_, dlw_, dlb_, wsp_):
-        if dx_add2 is not None and dx_ is not None:
-            rc = lib.rdst_ln_linear_bwd2(x.data_ptr(), ldx, _ptr(lw), _ptr(lb), _ptr(stats), in_act, _ptr(w),
-                                         dy.data_ptr(), lddy, _ptr(dx_), lddx, _ptr(add_), ld_add, _ptr(dw_), _ptr(db_),
-                                         _ptr(dlw_), _ptr(dlb_), wsp_.data_ptr(), nbytes, M, K, N, out_scale, code,
-                                         _stream(), dx_add2.data_ptr(), ld_add2)
-            if rc != _lib.ENOTSUP:
-                _lib.check(rc, "rdst_ln_linear_bwd2")
-                return
-        _lib.check(lib.rdst_ln_linear_bwd(x.data_ptr(), ldx, _ptr(lw), _ptr(lb), _ptr(stats), in_act, _ptr(w),
-                                          dy.data_ptr(), lddy, _ptr(dx_), lddx, _ptr(add_), ld_add, _ptr(dw_), _ptr(db_),
-                                          _ptr(dlw_), _ptr(dlb_), wsp_.data_ptr(), nbytes, M, K, N, out_scale, code,
-                                          _stream()), "rdst_ln_linear_bwd")
-        if dx_add2 is not None and dx_ is not None:
-            dx_.add_(dx_add2)
 
-    wgrad = dw is not None or db is not None
-    dgrad = dx is not None or dlw is not None or dlb is not None
-    if TWO_STREAM_BACKWARD and wgrad and dgrad:
-        cur, side = torch.cuda.current_stream(), _side_stream(dev)
-        wsp_w, wsp_d = _workspace(nbytes, dev), _workspace(nbytes, dev)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            call(None, None, dw, db, None, None, wsp_w)
-        call(dx, dx_add, None, None, dlw, dlb, wsp_d)
-        if join:
-            cur.wait_stream(side)
-        elif keep is not None:
-            keep.append(wsp_w)
-    elif wgrad or dgrad:
-        wsp = _workspace(nbytes, dev)
-        if keep is not None:   # a reduction batch is open: the slabs are read when it ends
-            keep.append(wsp)
-        call(dx, dx_add, dw, db, dlw, dlb, wsp)
+def _ln_linear_fwd(lib, x, ldx, lw, lb, in_act, w, b, res, ldr, y, ldy, stats, M, K, N, out_scale, code):
+    """The one launch site of rdst_ln_linear_fwd (x, res, y, stats: tensors or None).  Where the shape takes a packed
+    path, the weight image comes from the plan or is packed by the call itself (_packed_workspace)."""
+    wsp, wptr, nws = None, None, 0
+    if w is not None and (X3_STREAM or code != F32X3) and lib.rdst_ln_linear_fwd_packable(
+            K, N, int(lw is not None), int(res is not None), int(in_act), code):
+        nb = lib.rdst_ln_linear_fwd_workspace2(K, N, code)
+        wsp, wptr, nws = _packed_workspace([(_linear_pack_kind(code), w, lw, lb, b, N, K, out_scale, nb)], nb, x.device)
+    _lib.check(lib.rdst_ln_linear_fwd(x.data_ptr(), ldx, _ptr(lw), _ptr(lb), int(in_act), _ptr(w), _ptr(b), _ptr(res), ldr,
+                                      y.data_ptr(), ldy, _ptr(stats), wptr, nws, M, K, N, float(out_scale), code, _stream()),
+               "rdst_ln_linear_fwd")
+
+
+def _bias_grad(ctx, wanted: bool) -> Optional[torch.Tensor]:
+    """Destination of d(bias) of a Linear / conv node whose forward kept its fp32 bias (or None) in ``ctx.bias_ref``."""
+    return _grad_like(ctx.bias_ref) if (ctx.bias_ref is not None and wanted) else None
 
 
 # ------------------------------------------------------------------------------------------------
@@ -529,24 +498,16 @@ class _LnLinear(torch.autograd.Function):
             r_r, ldr = _rows(residual)
         stats = torch.empty((M, 2), dtype=torch.float32, device=x.device) if lw is not None else None
         code = _dtype_code(x)
-        if w is not None and (X3_STREAM or code != F32X3) and lib.rdst_ln_linear_fwd_packable(
-                K, N, int(lw is not None), int(r_r is not None), int(in_act), code):
-            _wsp, wptr, nws = _packed_workspace(_linear_pack_kind(code), w, lw, lb, b, N, K, out_scale,
-                                                lib.rdst_ln_linear_fwd_workspace2(K, N, code), x.device)
-        else:
-            _wsp, wptr, nws = None, None, 0
-        _lib.check(lib.rdst_ln_linear_fwd(x_r.data_ptr(), ldx, _ptr(lw), _ptr(lb), int(in_act), _ptr(w), _ptr(b),
-                                          _ptr(r_r), ldr, y.data_ptr(), ldy, _ptr(stats), wptr, nws, M, K, N,
-                                          float(out_scale), code, _stream()), "rdst_ln_linear_fwd")
+        _ln_linear_fwd(lib, x_r, ldx, lw, lb, in_act, w, b, r_r, ldr, y, ldy, stats, M, K, N, out_scale, code)
         ctx.save_for_backward(x_r, lw, lb, w, stats)
         ctx.bias_ref = b   # only its address is used in backward (destination lookup of d(bias))
-        ctx.meta = (M, K, N, ldx, int(in_act), float(out_scale), bias is not None, residual is not None, code)
+        ctx.meta = (M, K, N, ldx, int(in_act), float(out_scale), residual is not None, code)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, lw, lb, w, stats = ctx.saved_tensors
-        M, K, N, ldx, in_act, out_scale, has_bias, has_res, code = ctx.meta
+        M, K, N, ldx, in_act, out_scale, has_res, code = ctx.meta
         lib = _lib.load()
         dy_r, lddy = _rows(dy)
         need = ctx.needs_input_grad
@@ -555,8 +516,7 @@ class _LnLinear(torch.autograd.Function):
         dlw = _grad_like(lw) if (lw is not None and need[1]) else None
         dlb = _grad_like(lb) if (lb is not None and need[2]) else None
         dw = _grad_like(w) if (w is not None and need[3]) else None
-        db = (_grad_like(ctx.bias_ref) if ctx.bias_ref is not None
-              else _fresh_grad(torch.empty(N, dtype=torch.float32, device=dev))) if (has_bias and need[4]) else None
+        db = _bias_grad(ctx, need[4])
         _linear_bwd_call(lib, x, ldx, lw, lb, stats, in_act, w, dy_r, lddy, dx, K, None, 0, dw, db, dlw, dlb, M, K, N,
                          out_scale, code, dev, keep=_ReduceBatch.keep if _ReduceBatch.depth > 0 else None)
         _ReduceBatch.settle(lib)
@@ -598,126 +558,112 @@ class _IntoDense(torch.autograd.Function):
         return g, None
 
 
-class _ReduceBatchState(type):
-    """``_ReduceBatch.depth / .keep / .fresh`` live PER THREAD, like the C side's queues (csrc/reduce_batch.hip keeps
-    them ``thread_local``): autograd runs each device's backward on its own thread, so two devices in one process (or two
-    backward passes on two Python threads) never share a counter while their C queues are separate."""
-    _tls = threading.local()
-
-    def _state(cls):
-        st = cls._tls.__dict__
-        if "depth" not in st:
-            st.update(depth=0, keep=[], fresh=0, owner=-1, mixed=False, epoch=cls.EPOCH)
-        return st
-
-    # bumped by reset_backward_state(): a thread whose open batch was begun in an older epoch drops it (abort) before it
-    # queues, flushes or nests anything - how the main thread reaches the autograd device thread's batch after a failed pass
-    EPOCH = 0
-
-    depth = property(lambda cls: cls._state()["depth"], lambda cls, v: cls._state().__setitem__("depth", v))
-    keep = property(lambda cls: cls._state()["keep"], lambda cls, v: cls._state().__setitem__("keep", v))
-    fresh = property(lambda cls: cls._state()["fresh"], lambda cls, v: cls._state().__setitem__("fresh", v))
-    # the autograd graph task that opened the batch, and whether a node of ANOTHER task ran while it was open: the engine's
-    # device thread serves every concurrent backward() of that device, so nodes of two passes can interleave
-    owner = property(lambda cls: cls._state()["owner"], lambda cls, v: cls._state().__setitem__("owner", v))
-    mixed = property(lambda cls: cls._state()["mixed"], lambda cls, v: cls._state().__setitem__("mixed", v))
-    epoch = property(lambda cls: cls._state()["epoch"], lambda cls, v: cls._state().__setitem__("epoch", v))
-
-
-class _ReduceBatch(metaclass=_ReduceBatchState):
-    """Nesting-aware rdst_reduce_batch_begin / _end.  A Swin block's backward opens a batch for its own four ops; a
-    DenseSTLayer (dense join with a GradSink) opens an OUTER one in the join's backward — the first node of the layer's
-    backward — which the layer's first Swin block closes at the end of its own — the last node — so the slab sums and
-    LayerNorm finishes of the whole layer (two blocks + the tail Linear) run as 2 launches instead of 6.  `keep` holds
-    the ops' workspaces (the slabs) until the batch has run.
+class _ReduceBatchState(threading.local):
+    """Nesting-aware rdst_reduce_batch_begin / _end; ``_ReduceBatch`` below is its one instance.  A Swin block's backward
+    opens a batch for its own four ops; a DenseSTLayer (dense join with a GradSink) opens an OUTER one in the join's
+    backward — the first node of the layer's backward — which the layer's first Swin block closes at the end of its own —
+    the last node — so the slab sums and LayerNorm finishes of the whole layer (two blocks + the tail Linear) run as 2
+    launches instead of 6.  `keep` holds the ops' workspaces (the slabs) until the batch has run.
 
     A batch that spans autograd nodes defers WRITES of parameter gradients past the node that returns them.  That is
     only sound for destinations nobody reads before the batch ends: the flat-bucket views a detach_grads() bracket
     offers (rdst_amd.dp: p.grad is None, AccumulateGrad keeps the tensor without looking at it).  Any other destination
     (`fresh`: p.grad already defined -> autograd runs ``p.grad += g`` right after the node — bucket.zero() + backward,
     gradient accumulation, zero_grad(set_to_none=False) —, or a parameter used twice) makes the node `settle` before
-    it returns: the queued reductions run at once and the outer batch goes on empty."""
+    it returns: the queued reductions run at once and the outer batch goes on empty.
+
+    The state lives PER THREAD (a threading.local: every thread that touches it gets its own, set up by __init__), like
+    the C side's queues (csrc/reduce_batch.hip keeps them ``thread_local``): autograd runs each device's backward on its
+    own thread, so two devices in one process (or two backward passes on two Python threads) never share a counter while
+    their C queues are separate."""
+
+    # bumped by reset_backward_state(): a thread whose open batch was begun in an older epoch drops it (abort) before it
+    # queues, flushes or nests anything - how the main thread reaches the autograd device thread's batch after a failed pass
+    EPOCH = 0
+
+    def __init__(self):
+        self.depth, self.keep, self.fresh = 0, [], 0
+        # the autograd graph task that opened the batch, and whether a node of ANOTHER task ran while it was open: the engine's
+        # device thread serves every concurrent backward() of that device, so nodes of two passes can interleave
+        self.owner, self.mixed = -1, False
+        self.epoch = type(self).EPOCH
 
     @staticmethod
     def _task():
         return torch._C._current_graph_task_id()
 
-    @staticmethod
-    def _foreign():
+    def _foreign(self):
         """A node of another backward pass runs inside this thread's open batch (two Python threads called backward() on
         the same device at once): from here until the batch closes every node flushes what is queued before it returns,
         so no pass ever returns with reductions of its own still parked in the other pass's batch."""
-        if _ReduceBatch.depth > 0 and _ReduceBatch._task() != _ReduceBatch.owner:
-            _ReduceBatch.mixed = True
-        return _ReduceBatch.mixed
+        if self.depth > 0 and self._task() != self.owner:
+            self.mixed = True
+        return self.mixed
 
-    @staticmethod
-    def _drop_stale(lib):
+    def _drop_stale(self, lib):
         """This thread's batch was opened before the last reset_backward_state(): the pass it belonged to is dead."""
-        if _ReduceBatch.epoch != type(_ReduceBatch).EPOCH:
-            _ReduceBatch.abandon(lib)
-            _ReduceBatch.epoch = type(_ReduceBatch).EPOCH
+        if self.epoch != type(self).EPOCH:
+            self.abandon(lib)
+            self.epoch = type(self).EPOCH
 
-    @staticmethod
-    def begin(lib):
-        _ReduceBatch._drop_stale(lib)
-        if _ReduceBatch.depth == 0:
+    def _flush(self, lib):
+        """Run what is queued; the workspaces and scratch destinations it read are released whether it worked or not."""
+        try:
+            _lib.check(lib.rdst_reduce_batch_end(_stream()), "rdst_reduce_batch_end")
+        finally:
+            self.keep = []
+            self.fresh = 0
+
+    def begin(self, lib):
+        self._drop_stale(lib)
+        if self.depth == 0:
             _lib.check(lib.rdst_reduce_batch_begin(), "rdst_reduce_batch_begin")
-            _ReduceBatch.owner = _ReduceBatch._task()
-            _ReduceBatch.mixed = False
-        _ReduceBatch.depth += 1
+            self.owner = self._task()
+            self.mixed = False
+        self.depth += 1
 
-    @staticmethod
-    def begin_layer(lib):
+    def begin_layer(self, lib):
         """The dense join's outer batch (first node of a DenseSTLayer's backward).  Inside ONE pass no batch is open here,
         so an open one is either a leftover of this pass's task (a node raised and the pass was re-entered: drop it) or the
         batch of ANOTHER live pass served by the same device thread: that one keeps its queued reductions - this pass
         nests inside it and from here on every node flushes before it returns (`mixed`)."""
-        _ReduceBatch._drop_stale(lib)
-        if _ReduceBatch.depth > 0:
-            if _ReduceBatch.owner == _ReduceBatch._task():
-                _ReduceBatch.abandon(lib)
+        self._drop_stale(lib)
+        if self.depth > 0:
+            if self.owner == self._task():
+                self.abandon(lib)
             else:
-                _ReduceBatch.mixed = True
-        _ReduceBatch.begin(lib)
+                self.mixed = True
+        self.begin(lib)
 
-    @staticmethod
-    def end(lib, keep=None):
+    def end(self, lib, keep=None):
         if keep:
-            _ReduceBatch.keep.extend(keep)
-        _ReduceBatch.depth -= 1
-        if _ReduceBatch.depth == 0:
-            try:
-                _lib.check(lib.rdst_reduce_batch_end(_stream()), "rdst_reduce_batch_end")
-            finally:
-                _ReduceBatch.keep = []
-                _ReduceBatch.fresh = 0
+            self.keep.extend(keep)
+        self.depth -= 1
+        if self.depth == 0:
+            self._flush(lib)
 
-    @staticmethod
-    def settle(lib):
+    def settle(self, lib):
         """Last statement of a node's backward: if a batch is still open around this node and the node handed out a
         gradient destination that autograd may read on return, run what is queued now (and keep the batch open)."""
-        _ReduceBatch._drop_stale(lib)
-        if _ReduceBatch.depth > 0 and (_ReduceBatch.fresh or _ReduceBatch._foreign()):
-            try:
-                _lib.check(lib.rdst_reduce_batch_end(_stream()), "rdst_reduce_batch_end")
-            finally:
-                _ReduceBatch.keep = []
-                _ReduceBatch.fresh = 0
+        self._drop_stale(lib)
+        if self.depth > 0 and (self.fresh or self._foreign()):
+            self._flush(lib)
             _lib.check(lib.rdst_reduce_batch_begin(), "rdst_reduce_batch_begin")
-        elif _ReduceBatch.depth == 0:
-            _ReduceBatch.fresh = 0
+        elif self.depth == 0:
+            self.fresh = 0
 
-    @staticmethod
-    def abandon(lib):
+    def abandon(self, lib):
         """Forget whatever a failed / partial backward left open: its queued reductions are DROPPED — the slabs and the
         outputs they name belonged to that backward and may be freed (rdst_reduce_batch_abort)."""
-        if _ReduceBatch.depth > 0:
+        if self.depth > 0:
             _lib.check(lib.rdst_reduce_batch_abort(), "rdst_reduce_batch_abort")
-        _ReduceBatch.depth = 0
-        _ReduceBatch.keep = []
-        _ReduceBatch.fresh = 0
-        _ReduceBatch.mixed = False
+        self.depth = 0
+        self.keep = []
+        self.fresh = 0
+        self.mixed = False
+
+
+_ReduceBatch = _ReduceBatchState()
 
 
 def reset_backward_state() -> None:
@@ -761,7 +707,7 @@ class _DenseJoin(torch.autograd.Function):
     def backward(ctx, g):
         if ctx.sink is not None and ctx.needs_input_grad[0]:
             ctx.sink.extra = g[..., :ctx.c]
-            if g.is_cuda and not TWO_STREAM_BACKWARD:
+            if g.is_cuda:
                 lib = _lib.load()
                 _ReduceBatch.begin_layer(lib)
                 ctx.sink.batch_open = True
@@ -814,17 +760,6 @@ class _SwinBlock(torch.autograd.Function):
         n1w_, n1b_, qkvw_, qkvb_, tab_, projw_, projb_, n2w_, n2b_, fc1w_, fc1b_, fc2w_, fc2b_ = P
         lead = x.shape[:-1]
         st = _stream()
-
-        def lin(xp, ld, lw, lb, act, w, b, rp, ldr, out, N, stats, K):
-            if (X3_STREAM or code != F32X3) and lib.rdst_ln_linear_fwd_packable(K, N, int(lw is not None), int(rp is not None), act, code):
-                _wsp, wptr, nws = _packed_workspace(_linear_pack_kind(code), w, lw, lb, b, N, K, 1.0,
-                                                    lib.rdst_ln_linear_fwd_workspace2(K, N, code), dev)
-            else:
-                _wsp, wptr, nws = None, None, 0
-            _lib.check(lib.rdst_ln_linear_fwd(xp, ld, _ptr(lw), _ptr(lb), act, w.data_ptr(), _ptr(b), rp, ldr,
-                                              out.data_ptr(), N, _ptr(stats), wptr, nws, M, K, N, 1.0, code, st),
-                       "rdst_ln_linear_fwd")
-
         stats1 = torch.empty((M, 2), dtype=torch.float32, device=dev) if n1w_ is not None else None
         qkv = torch.empty(lead + (3 * C,), dtype=dt, device=dev)
         a = torch.empty(lead + (C,), dtype=dt, device=dev)
@@ -833,17 +768,10 @@ class _SwinBlock(torch.autograd.Function):
                       and bool(lib.rdst_swin_attn_fwd_supported(C, heads, ws, code)))
         if fused_attn:
             # K8: norm1 + qkv -> window attention -> proj + shortcut as ONE launch (qkv, a, x1, stats1 for the backward)
-            nbytes = lib.rdst_swin_attn_fwd_workspace(C)
-            wptr, nws, _wsp = None, 0, None
-            if _plan_active is not None:
-                wptr = _plan_active.lookup_swinattn(qkvw_, n1w_, n1b_, qkvb_, projw_, projb_)
-                nws = _lib.PREPACKED
-            if wptr is None:
-                nbp = lib.rdst_ln_linear_fwd_workspace(C, C)
-                if _plan_recording is not None:
-                    _plan_recording.record_swinattn(qkvw_, n1w_, n1b_, qkvb_, projw_, projb_, C, nbytes - nbp, nbp)
-                _wsp = _workspace(nbytes, dev)
-                wptr, nws = _wsp.data_ptr(), nbytes
+            # its workspace: the sectioned qkv image (norm1 folded in), then the proj image
+            nbytes, nbp = lib.rdst_swin_attn_fwd_workspace(C), lib.rdst_ln_linear_fwd_workspace(C, C)
+            _wsp, wptr, nws = _packed_workspace([(PACK_LINEAR_SEC3, qkvw_, n1w_, n1b_, qkvb_, 3 * C, C, 1.0, nbytes - nbp),
+                                                 (PACK_LINEAR, projw_, None, None, projb_, C, C, 1.0, nbp)], nbytes, dev)
             rc = lib.rdst_swin_attn_fwd(x_r.data_ptr(), ldx, n1w_.data_ptr(), n1b_.data_ptr(), qkvw_.data_ptr(), _ptr(qkvb_),
                                         tab_.data_ptr(), projw_.data_ptr(), _ptr(projb_), qkv.data_ptr(), 3 * C, a.data_ptr(), C,
                                         x1.data_ptr(), C, stats1.data_ptr(), wptr, nws, B, H, W, C, heads, ws, shift,
@@ -854,7 +782,7 @@ class _SwinBlock(torch.autograd.Function):
                 _lib.check(rc, "rdst_swin_attn_fwd")
         nlse = None
         if not fused_attn:
-            lin(x_r.data_ptr(), ldx, n1w_, n1b_, ACT_NONE, qkvw_, qkvb_, None, 0, qkv, 3 * C, stats1, C)
+            _ln_linear_fwd(lib, x_r, ldx, n1w_, n1b_, ACT_NONE, qkvw_, qkvb_, None, 0, qkv, 3 * C, stats1, M, C, 3 * C, 1.0, code)
             if ATTN_LSE and ws == 16 and code == BF16:
                 # window 16: keep the row statistics, the backward's first pass then streams its key tiles (rdst_wattn_bwd_lse)
                 nlse = torch.empty((M, heads), dtype=torch.float32, device=dev)
@@ -867,25 +795,19 @@ class _SwinBlock(torch.autograd.Function):
             if nlse is None:
                 _lib.check(lib.rdst_wattn_fwd(qkv.data_ptr(), 3 * C, tab_.data_ptr(), None, 0, a.data_ptr(), C, B, H, W, C,
                                               heads, ws, shift, float(scale), code, _stream()), "rdst_wattn_fwd")
-            lin(a.data_ptr(), C, None, None, ACT_NONE, projw_, projb_, x_r.data_ptr(), ldx, x1, C, None, C)
+            _ln_linear_fwd(lib, a, C, None, None, ACT_NONE, projw_, projb_, x_r, ldx, x1, C, None, M, C, C, 1.0, code)
         stats2 = torch.empty((M, 2), dtype=torch.float32, device=dev) if n2w_ is not None else None
         y = torch.empty(lead + (C,), dtype=dt, device=dev)
         h = None
         fused_mlp = MLP_FUSED and n2w_ is not None and bool(lib.rdst_mlp_fused_supported(C, hid, code))
         if fused_mlp:
             # K7: the whole Mlp half in one kernel; the hidden activations are not kept (the backward recomputes them)
-            wptr, nws, _wsp = None, 0, None
-            if lib.rdst_mlp_fwd_packable(C, hid, code):
-                nb1, nb2 = lib.rdst_ln_linear_fwd_workspace(C, hid), lib.rdst_ln_linear_fwd_workspace(hid, C)
-                if _plan_active is not None:
-                    wptr = _plan_active.lookup_mlp(fc1w_, n2w_, n2b_, fc1b_, fc2w_, fc2b_)
-                    nws = _lib.PREPACKED
-                if wptr is None:
-                    if _plan_recording is not None:
-                        _plan_recording.record_mlp(fc1w_, n2w_, n2b_, fc1b_, fc2w_, fc2b_, C, hid, nb1, nb2)
-                    nws = lib.rdst_mlp_fwd_workspace(C, hid)
-                    _wsp = _workspace(nws, dev)
-                    wptr = _wsp.data_ptr()
+            _wsp, wptr, nws = None, None, 0
+            if lib.rdst_mlp_fwd_packable(C, hid, code):   # its workspace: two Linear images, fc1 (norm2 folded in), then fc2
+                _wsp, wptr, nws = _packed_workspace(
+                    [(PACK_LINEAR, fc1w_, n2w_, n2b_, fc1b_, hid, C, 1.0, lib.rdst_ln_linear_fwd_workspace(C, hid)),
+                     (PACK_LINEAR, fc2w_, None, None, fc2b_, C, hid, 1.0, lib.rdst_ln_linear_fwd_workspace(hid, C))],
+                    lib.rdst_mlp_fwd_workspace(C, hid), dev)
             rc = lib.rdst_mlp_fwd(x1.data_ptr(), C, n2w_.data_ptr(), n2b_.data_ptr(), fc1w_.data_ptr(), _ptr(fc1b_),
                                   fc2w_.data_ptr(), _ptr(fc2b_), y.data_ptr(), C, stats2.data_ptr(), wptr, nws, M, C, hid, code, st)
             if rc == _lib.ENOTSUP:
@@ -894,8 +816,8 @@ class _SwinBlock(torch.autograd.Function):
                 _lib.check(rc, "rdst_mlp_fwd")
         if not fused_mlp:
             h = torch.empty(lead + (hid,), dtype=dt, device=dev)
-            lin(x1.data_ptr(), C, n2w_, n2b_, ACT_NONE, fc1w_, fc1b_, None, 0, h, hid, stats2, C)
-            lin(h.data_ptr(), hid, None, None, ACT_GELU, fc2w_, fc2b_, x1.data_ptr(), C, y, C, None, hid)
+            _ln_linear_fwd(lib, x1, C, n2w_, n2b_, ACT_NONE, fc1w_, fc1b_, None, 0, h, hid, stats2, M, C, hid, 1.0, code)
+            _ln_linear_fwd(lib, h, hid, None, None, ACT_GELU, fc2w_, fc2b_, x1, C, y, C, None, M, hid, C, 1.0, code)
         ctx.save_for_backward(x_r, stats1, qkv, a, x1, stats2, h, nlse, *P)
         ctx.meta = (M, B, H, W, C, hid, heads, ws, shift, float(scale), ldx, code)
         return y
@@ -917,22 +839,17 @@ class _SwinBlock(torch.autograd.Function):
         dprojw, dprojb = g(projw, need[6]), g(projb, need[7])
         dn2w, dn2b, dfc1w, dfc1b = g(n2w, need[8]), g(n2b, need[9]), g(fc1w, need[10]), g(fc1b, need[11])
         dfc2w, dfc2b = g(fc2w, need[12]), g(fc2b, need[13])
-        # The four weight-gradient kernels are leaves: they go to the side stream and are joined ONCE at the
-        # end of this block's backward, so they overlap the whole data-gradient chain below.  Everything they
-        # read (saved activations, dy, dh, dx1, dqkv, their workspaces) stays referenced until then.
+        # the slab reductions of the four ops below are recorded and run as two launches when the batch ends
+        # (rdst_reduce_batch_*); everything they read (the ops' workspaces, scratch destinations, copies) is parked in
+        # `keep`, which the batch holds until it has run
         keep = []
-        # the slab reductions of the four ops below are recorded and run as two launches at the end (rdst_reduce_batch_*);
-        # their workspaces are locals of this function, alive until then
-        batched = not TWO_STREAM_BACKWARD
-        outer = batched and ctx.sink is not None and ctx.sink.take_batch()   # this block ends its DenseSTLayer's batch too
-        if batched:
-            _ReduceBatch.begin(lib)
+        outer = ctx.sink is not None and ctx.sink.take_batch()   # this block ends its DenseSTLayer's batch too
+        _ReduceBatch.begin(lib)
         try:
             return _SwinBlock._backward_body(ctx, lib, dy_r, lddy, need, keep, dn1w, dn1b, dqkvw, dqkvb, dprojw, dprojb, dn2w,
                                              dn2b, dfc1w, dfc1b, dfc2w, dfc2b)
         finally:
-            if batched:
-                _ReduceBatch.end(lib, keep)
+            _ReduceBatch.end(lib, keep)
             if outer:
                 _ReduceBatch.end(lib)
             _ReduceBatch.settle(lib)   # (a later block of a DenseSTLayer: the layer's batch is still open around it)
@@ -962,20 +879,20 @@ class _SwinBlock(torch.autograd.Function):
             nb = lib.rdst_mlp_bwd_workspace(M, C, hid)
             wsp_m = _workspace(nb, dev)
             keep.append(wsp_m)   # read by the batched reductions at the end of backward()
-            rc = lib.rdst_mlp_bwd(x1.data_ptr(), C, n2w.data_ptr(), n2b.data_ptr(), stats2.data_ptr(), fc1w.data_ptr(),
-                                  _ptr(fc1b), fc2w.data_ptr(), dy_r.data_ptr(), lddy, dx1.data_ptr(), C,
-                                  o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), o[3].data_ptr(), o[4].data_ptr(),
-                                  o[5].data_ptr(), wsp_m.data_ptr(), nb, M, C, hid, code, _stream())
+
+            def mlp_bwd(dy_, ld_):
+                return lib.rdst_mlp_bwd(x1.data_ptr(), C, n2w.data_ptr(), n2b.data_ptr(), stats2.data_ptr(), fc1w.data_ptr(),
+                                        _ptr(fc1b), fc2w.data_ptr(), dy_.data_ptr(), ld_, dx1.data_ptr(), C,
+                                        o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), o[3].data_ptr(), o[4].data_ptr(),
+                                        o[5].data_ptr(), wsp_m.data_ptr(), nb, M, C, hid, code, _stream())
+            rc = mlp_bwd(dy_r, lddy)
             if rc == _lib.ENOTSUP and h is None:
                 # The forward ran fused (h was never written), so there is no composed path to fall back to; what the
                 # kernel can refuse at this point is the ALIGNMENT of dy (a strided gradient slice with an odd channel
                 # offset): hand it an aligned contiguous copy (ld = C) — same kernel, same result.
                 dy_c = dy_r.clone(memory_format=torch.contiguous_format)
                 keep.append(dy_c)
-                rc = lib.rdst_mlp_bwd(x1.data_ptr(), C, n2w.data_ptr(), n2b.data_ptr(), stats2.data_ptr(), fc1w.data_ptr(),
-                                      _ptr(fc1b), fc2w.data_ptr(), dy_c.data_ptr(), C, dx1.data_ptr(), C,
-                                      o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), o[3].data_ptr(), o[4].data_ptr(),
-                                      o[5].data_ptr(), wsp_m.data_ptr(), nb, M, C, hid, code, _stream())
+                rc = mlp_bwd(dy_c, C)
             if rc == _lib.ENOTSUP and h is not None:
                 fused_mlp = False
             else:
@@ -984,14 +901,14 @@ class _SwinBlock(torch.autograd.Function):
             # fc2 (reads h through GELU):  dh = (dy W2) * gelu'(h)
             dh = torch.empty_like(h)
             _linear_bwd_call(lib, h, hid, None, None, None, ACT_GELU, fc2w, dy_r, lddy, dh, hid, None, 0, dfc2w, dfc2b,
-                             None, None, M, hid, C, 1.0, code, dev, join=False, keep=keep)
+                             None, None, M, hid, C, 1.0, code, dev, keep=keep)
             # LN2 + fc1, plus the residual fan-out of x1:  dx1 = dy + LN2'(dh W1)
             _linear_bwd_call(lib, x1, C, n2w, n2b, stats2, ACT_NONE, fc1w, dh, hid, dx1, C, dy_r, lddy, dfc1w, dfc1b,
-                             dn2w, dn2b, M, C, hid, 1.0, code, dev, join=False, keep=keep)
+                             dn2w, dn2b, M, C, hid, 1.0, code, dev, keep=keep)
         # proj:  da = dx1 Wp
         da = torch.empty_like(a)
         _linear_bwd_call(lib, a, C, None, None, None, ACT_NONE, projw, dx1, C, da, C, None, 0, dprojw, dprojb, None, None,
-                         M, C, C, 1.0, code, dev, join=False, keep=keep)
+                         M, C, C, 1.0, code, dev, keep=keep)
         # window attention
         dqkv = torch.empty_like(qkv)
         dtab = _grad_like(tab)
@@ -1018,10 +935,8 @@ class _SwinBlock(torch.autograd.Function):
         else:
             extra, ld_extra = None, 0
         _linear_bwd_call(lib, x, ldx, n1w, n1b, stats1, ACT_NONE, qkvw, dqkv, 3 * C, dx, C, dx1 if need[0] else None, C,
-                         dqkvw, dqkvb, dn1w, dn1b, M, C, 3 * C, 1.0, code, dev, join=False, keep=keep, dx_add2=extra,
+                         dqkvw, dqkvb, dn1w, dn1b, M, C, 3 * C, 1.0, code, dev, keep=keep, dx_add2=extra,
                          ld_add2=ld_extra)
-        if TWO_STREAM_BACKWARD:
-            torch.cuda.current_stream().wait_stream(_side_stream(dev))   # the one join of this block
         if not need[5]:
             dtab = None
         return (dx, dn1w, dn1b, dqkvw, dqkvb, dtab, dprojw, dprojb, dn2w, dn2b, dfc1w, dfc1b, dfc2w, dfc2b,
@@ -1065,50 +980,35 @@ class _ConvRows(torch.autograd.Function):
                 raise ValueError("rdst_amd.conv_rows: residual must match the output shape/dtype")
             r_r, ldr = _rows(residual)
         code = _dtype_code(x)
+        _wsp, wptr, nws = None, None, 0
         if (X3_STREAM or code != F32X3) and lib.rdst_conv_fwd_packable(Cin, Cout, k, r, int(r_r is not None), int(in_act), code):
-            _wsp, wptr, nws = _packed_workspace(PACK_CONV3_FWD_X3 if code == F32X3 else PACK_CONV3_FWD, w, None, None, None, Cout, Cin,
-                                                out_scale, lib.rdst_conv_fwd_workspace2(Cin, Cout, k, code), x.device)
-        else:
-            _wsp, wptr, nws = None, None, 0
+            nb = lib.rdst_conv_fwd_workspace2(Cin, Cout, k, code)
+            _wsp, wptr, nws = _packed_workspace([(PACK_CONV3_FWD_X3 if code == F32X3 else PACK_CONV3_FWD, w, None, None, None, Cout,
+                                                  Cin, out_scale, nb)], nb, x.device)
         _lib.check(lib.rdst_conv_fwd(x_r.data_ptr(), ldx, int(in_act), w.data_ptr(), _ptr(b), _ptr(r_r), ldr,
                                      y.data_ptr(), ldy, wptr, nws, B, H, W, Cin, Cout, k, float(out_scale), r,
                                      code, _stream()), "rdst_conv_fwd")
         ctx.bias_ref = b   # only its address is used in backward (destination lookup of d(bias))
         ctx.save_for_backward(x_r, w)
-        ctx.meta = (B, H, W, Cin, Cout, k, ldx, int(in_act), float(out_scale), r, bias is not None,
-                    residual is not None, code)
+        ctx.meta = (B, H, W, Cin, Cout, k, ldx, int(in_act), float(out_scale), r, residual is not None, code)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        B, H, W, Cin, Cout, k, ldx, in_act, out_scale, r, has_bias, has_res, code = ctx.meta
+        B, H, W, Cin, Cout, k, ldx, in_act, out_scale, r, has_res, code = ctx.meta
         lib = _lib.load()
         dy_r, lddy = _rows(dy)
         need = ctx.needs_input_grad
         dev = x.device
         dx = torch.empty((B, H, W, Cin), dtype=x.dtype, device=dev) if need[0] else None
         dw = _grad_like(w) if need[1] else None
-        db = (_grad_like(ctx.bias_ref) if ctx.bias_ref is not None
-              else _fresh_grad(torch.empty(Cout, dtype=torch.float32, device=dev))) if (has_bias and need[2]) else None
+        db = _bias_grad(ctx, need[2])
         nbytes = lib.rdst_conv_bwd_workspace(B, H, W, Cin, Cout, k)
-
-        def call(dx_, dw_, db_, wsp_):
-            _lib.check(lib.rdst_conv_bwd(x.data_ptr(), ldx, in_act, w.data_ptr(), dy_r.data_ptr(), lddy, _ptr(dx_), Cin,
-                                         None, 0, _ptr(dw_), _ptr(db_), wsp_.data_ptr(), nbytes, B, H, W, Cin, Cout, k,
-                                         out_scale, r, code, _stream()), "rdst_conv_bwd")
-
-        if TWO_STREAM_BACKWARD and dx is not None and (dw is not None or db is not None):
-            cur, side = torch.cuda.current_stream(), _side_stream(dev)
-            wsp_w = _workspace(nbytes, dev)
-            wsp_d = _workspace(nbytes, dev)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                call(None, dw, db, wsp_w)
-            call(dx, None, None, wsp_d)
-            cur.wait_stream(side)
-        else:
-            call(dx, dw, db, _workspace(nbytes, dev))
+        wsp = _workspace(nbytes, dev)
+        _lib.check(lib.rdst_conv_bwd(x.data_ptr(), ldx, in_act, w.data_ptr(), dy_r.data_ptr(), lddy, _ptr(dx), Cin,
+                                     None, 0, _ptr(dw), _ptr(db), wsp.data_ptr(), nbytes, B, H, W, Cin, Cout, k,
+                                     out_scale, r, code, _stream()), "rdst_conv_bwd")
         _ReduceBatch.settle(lib)   # (a conv inside an open outer batch: nothing of its own is deferred, its fresh destinations settle)
         dres = dy if (has_res and need[3]) else None
         return dx, dw, db, dres, None, None, None, None

@@ -1,4 +1,5 @@
-"""Which ops of an RDST-E1 forward find their packed weight image in the PackPlan, and which pack for themselves.
+"""Which ops of an RDST-E1 forward find their packed weight images in the PackPlan, and which pack for themselves: Linear and
+conv (one image each) and the fused Swin-block halves (K7: fc1 + fc2, K8: sectioned qkv + proj), one line per group of images.
 Run on the GPU box: python tools/pack_audit.py"""
 import collections, sys, torch
 sys.path.insert(0, ".")
@@ -12,9 +13,10 @@ orig = ops._packed_workspace
 log = collections.Counter()
 
 
-def audit(kind, w, lw, lb, b, N, K, s, nbytes, device):
-    r = orig(kind, w, lw, lb, b, N, K, s, nbytes, device)
-    log[(kind, N, K, round(float(s), 6), "plan" if r[2] == _lib.PREPACKED else "self")] += 1
+def audit(images, nbytes, device):
+    r = orig(images, nbytes, device)
+    group = tuple((kind, N, K, round(float(s), 6)) for kind, _w, _lw, _lb, _b, N, K, s, _nb in images)
+    log[group + ("plan" if r[2] == _lib.PREPACKED else "self",)] += 1
     return r
 
 
