@@ -299,6 +299,32 @@ int rdst_reduce_batch_end(void* stream);
  * outputs the jobs name may already be freed).  No-op without an open batch.  (ABI 7) */
 int rdst_reduce_batch_abort(void);
 
+/* ---- the side branch of the deferred reductions -------------------------------------------------
+ * Nothing on the backward chain reads what rdst_reduce_batch_end() computes (parameter gradients) before the
+ * optimizer does, so its two launches need not sit on that chain.  With the side branch enabled, _end(stream)
+ *   (a) makes `stream` wait for the event that closed the previous generation of side work,
+ *   (b) records an event on `stream` and makes the device's side stream (one, non-blocking) wait for it,
+ *   (c) launches the queued sums, then the finishes, on the side stream: same kernels, same job order, same summation order,
+ *   (d) records the generation's closing event on the side stream,
+ * and returns; `stream` goes on with the next layer.  What the launches read must stay alive until the NEXT _end() (whose
+ * step (a) orders `stream` behind them) or rdst_side_join() has returned.  The stream and a small ring of timing-disabled
+ * events are created on the first enabled _end() outside stream capture, never inside one; until they exist an _end() on a
+ * capturing stream takes the serial path.  Events are the only ordering: inside a capture the branch becomes one parallel
+ * branch of the graph, and rdst_side_join() must rejoin it before the capture ends.
+ * The switch is process-wide (autograd runs the backward on its own thread); the state is per device. */
+/* Bit 1 of `on`: the reductions as above.  Bit 2: rdst_conv_bwd, where both the data and the weight gradient are wanted,
+ * issues its register-stationary / one-channel weight-gradient kernels (and their reduce) on the side stream behind an event
+ * recorded at entry, beside its data-gradient kernel; X, dY and the workspace then have to stay alive like a generation's slabs,
+ * and dW / dbias are complete after the next _end() on `stream` or a join.  With bit 2 alone _end() keeps its launches on
+ * `stream` and only does step (a). */
+int rdst_side_enable(int on);      /* returns the previous value; touches no HIP call */
+/* `stream` waits for everything issued on the side stream of its device; callable during capture.  No-op with nothing pending. */
+int rdst_side_join(void* stream);
+/* Leave no generation pending (after a backward that died half way): the host waits for side work that was issued eagerly,
+ * side work recorded in a capture is forgotten.  rdst_reduce_batch_abort() does the same.  Returns 0 and touches no HIP
+ * call where nothing was ever created (no device). */
+int rdst_side_reset(void);
+
 /* ---- layout helpers at the NCHW boundary of the module ------------------------------------------
  * nchw (B,C,H,W) fp32 <-> token rows (B*H*W, C) of `dtype`.  The caller-facing tensors of
  * RDSTSR.forward are fp32 NCHW (rdst_variations.py:1342-1360). */

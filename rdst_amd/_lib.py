@@ -65,6 +65,9 @@ SIGNATURES = {
     "rdst_reduce_batch_begin": (_i, []),
     "rdst_reduce_batch_end": (_i, [_p]),
     "rdst_reduce_batch_abort": (_i, []),
+    "rdst_side_enable": (_i, [_i]),
+    "rdst_side_join": (_i, [_p]),
+    "rdst_side_reset": (_i, []),
     "rdst_wattn_fwd_drop": (_i, [_p, _l, _p, _p, _i, _p, _l, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _p, _p]),
     "rdst_wattn_bwd_drop": (_i, [_p, _l, _p, _p, _i, _p, _l, _p, _l, _p, _p, _z, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _p, _p]),
     "rdst_wattn_drop_mask": (_i, [_p, _i, _i, _i, _i, _i, _f, _p, _p]),

@@ -53,7 +53,7 @@ int conv_c1_fwd_bf16(const bf16* X, int64_t ldx, int in_act, const float* Wc, co
                      int64_t ldy, const ConvGeom& g, float s, hipStream_t st);
 int conv_c1_bwd_bf16(const bf16* X, int64_t ldx, int in_act, const float* Wc, const bf16* dY, int64_t lddy, bf16* dX,
                      int64_t lddx, const bf16* acc, int64_t ldacc, float* dW, float* dbias, float* slab, const ConvGeom& g,
-                     float s, hipStream_t st);
+                     float s, hipStream_t st, hipStream_t wst);
 size_t conv_c1_slab_floats(int Cin);
 // the mirror shape, one INPUT channel -> Cout (the head conv on a single-channel image), bf16: forward and weight gradient
 // on the same tile kernels; RDST_ENOTSUP for other shapes

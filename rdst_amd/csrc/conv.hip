@@ -6,6 +6,7 @@
 #include "common.h"
 #include "gemm_valu.h"
 #include "conv.h"
+#include "reduce_batch.h"
 
 namespace {
 
@@ -150,9 +151,12 @@ int fwd_t(const T* X, int64_t ldx, int in_act, const float* Wc, const float* bia
   return gemm_valu_launch(la, lb, ep, g.pixels(), g.Cout, (int64_t)g.ks * g.ks * g.Cin, 1, st, "conv_fwd");
 }
 
+// `wst`: the stream of the register-stationary weight-gradient kernels and their reduce, which read X and dY as they lie and
+// nothing the data-gradient kernels write: `st`, or the side stream (bwd_t)
 template <typename T>
-int bwd_t(const T* X, int64_t ldx, int in_act, const float* Wc, const T* dY, int64_t lddy, T* dX, int64_t lddx,
-          const T* acc, int64_t ldacc, float* dW, float* dbias, float* wsp, const ConvGeom& g, float s, bool split, hipStream_t st) {
+int bwd_impl(const T* X, int64_t ldx, int in_act, const float* Wc, const T* dY, int64_t lddy, T* dX, int64_t lddx,
+             const T* acc, int64_t ldacc, float* dW, float* dbias, float* wsp, const ConvGeom& g, float s, bool split, hipStream_t st,
+             hipStream_t wst) {
   const int64_t wtotal = (int64_t)g.Cout * g.Cin * g.ks * g.ks;
   // workspace carve: [packed dgrad weights][generic split-K slab][small][MFMA scratch: un-shuffled dY, wgrad slab]
   void* wpack = wsp;
@@ -164,7 +168,7 @@ int bwd_t(const T* X, int64_t ldx, int in_act, const float* Wc, const T* dY, int
   char* mscr = reinterpret_cast<char*>(small + (int64_t)kSmallBlocks * g.Cout + 64);
   if constexpr (sizeof(T) == 2) {   // the one-output-channel tail conv: vector kernels, its own slab at the end of the workspace
     float* c1slab = reinterpret_cast<float*>(mscr + conv_mfma_scratch_bytes(ConvGeom{g.B, g.H, g.W, g.Cin, g.Cout, g.ks, g.pad, 2}));
-    if (int rc = conv_c1_bwd_bf16(X, ldx, in_act, Wc, dY, lddy, dX, lddx, acc, ldacc, dW, dbias, c1slab, g, s, st); rc != RDST_ENOTSUP)
+    if (int rc = conv_c1_bwd_bf16(X, ldx, in_act, Wc, dY, lddy, dX, lddx, acc, ldacc, dW, dbias, c1slab, g, s, st, wst); rc != RDST_ENOTSUP)
       return rc;
     if (!dX && (dW || dbias) && g.r == 1) {   // one input channel (the head conv: no data gradient, the input is the image)
       if (int rc = conv_in1_wgrad_bf16(X, ldx, in_act, dY, lddy, dW, dbias, c1slab, g, s, st); rc != RDST_ENOTSUP) return rc;
@@ -186,7 +190,7 @@ int bwd_t(const T* X, int64_t ldx, int in_act, const float* Wc, const T* dY, int
       else if (rc != RDST_ENOTSUP) return rc;
     }
     if (dW || dbias) {
-      const int rc = conv3_wgrad_bf16(X, ldx, in_act, dY, lddy, dW, dbias, w3slab, g, s, st);
+      const int rc = conv3_wgrad_bf16(X, ldx, in_act, dY, lddy, dW, dbias, w3slab, g, s, wst);
       if (rc == 0) { dW = nullptr; dbias = nullptr; }
       else if (rc != RDST_ENOTSUP) return rc;
     }
@@ -199,7 +203,7 @@ int bwd_t(const T* X, int64_t ldx, int in_act, const float* Wc, const T* dY, int
       else if (rc != RDST_ENOTSUP) return rc;
     }
     if ((dW || dbias) && split) {   // ... and weight gradient (conv3x_wgrad.hip): the shuffled dY as it lies
-      const int rc = conv3x_wgrad_f32(X, ldx, in_act, dY, lddy, dW, dbias, w3slab, g, s, st);
+      const int rc = conv3x_wgrad_f32(X, ldx, in_act, dY, lddy, dW, dbias, w3slab, g, s, wst);
       if (rc == 0) { dW = nullptr; dbias = nullptr; }
       else if (rc != RDST_ENOTSUP) return rc;
     }
@@ -242,6 +246,20 @@ int bwd_t(const T* X, int64_t ldx, int in_act, const float* Wc, const T* dY, int
     if (rc) return rc;
   }
   return 0;
+}
+
+// With the side branch's conv stage on (reduce_batch.h) and both gradients wanted, the weight gradient runs beside the data
+// gradient: forked behind an event recorded here, at entry.
+template <typename T>
+int bwd_t(const T* X, int64_t ldx, int in_act, const float* Wc, const T* dY, int64_t lddy, T* dX, int64_t lddx,
+          const T* acc, int64_t ldacc, float* dW, float* dbias, float* wsp, const ConvGeom& g, float s, bool split, hipStream_t st) {
+  rside::Fork f;
+  f.run = st;
+  if (dX && (dW || dbias))
+    if (int rc = rside::fork_begin(st, f)) return rc;
+  int rc = bwd_impl<T>(X, ldx, in_act, Wc, dY, lddy, dX, lddx, acc, ldacc, dW, dbias, wsp, g, s, split, st, f.run);
+  const int rc2 = rside::fork_end(f);
+  return rc ? rc : rc2;
 }
 
 int make_geom(ConvGeom& g, int B, int H, int W, int Cin, int Cout, int ks, int r, const char* who) {

@@ -517,9 +517,10 @@ int conv_in1_wgrad_bf16(const bf16* X, int64_t ldx, int in_act, const bf16* dY, 
 }
 
 // dW (1, Cin, 3, 3), dbias (1), dX (optional) of the one-output-channel conv; slab >= conv_c1_slab_floats()
+// The weight gradient, its reduce and its two copies go to `wst` (they read X, dY and the slab alone), the data gradient to `st`.
 int conv_c1_bwd_bf16(const bf16* X, int64_t ldx, int in_act, const float* Wc, const bf16* dY, int64_t lddy, bf16* dX,
                      int64_t lddx, const bf16* acc, int64_t ldacc, float* dW, float* dbias, float* slab, const ConvGeom& g,
-                     float s, hipStream_t st) {
+                     float s, hipStream_t st, hipStream_t wst) {
   if (g.Cin == 1 && g.Cout == 1 && g.ks == 1 && g.r == 1 && in_act == 0 && !dW && !dbias && dX)   // frozen MeanShift: dX = dY w s (+ dX_add)
     return pw11_launch(dY, lddy, Wc, nullptr, acc, ldacc, dX, lddx, g.pixels(), s, st, "conv_pw11_dgrad");
   if (!c1_ok(g, in_act) || ((uintptr_t)X & 3) || (ldx & 1) || ((uintptr_t)dX & 3) || (lddx & 1) || ((uintptr_t)acc & 3) || (ldacc & 1))
@@ -529,14 +530,14 @@ int conv_c1_bwd_bf16(const bf16* X, int64_t ldx, int in_act, const float* Wc, co
   p.g = g; p.s = s; p.slab = slab;
   if (dW || dbias) {
     const int grid = c1_grid(p, 1024);
-    hipLaunchKernelGGL(conv_c1_wgrad_kernel<false>, dim3(grid), dim3(C1_THREADS), 0, st, p);
+    hipLaunchKernelGGL(conv_c1_wgrad_kernel<false>, dim3(grid), dim3(C1_THREADS), 0, wst, p);
     if (int rc = rdst_launch_status("conv_c1_wgrad")) return rc;
     const int n = g.Cin * 9;
     // one reduction over [grid][n + 1]: dW then dbias are contiguous in the slab row; the destinations are not
     float* red = slab + (size_t)grid * (n + 1);
-    if (int rc = slab_reduce(slab, red, grid, n + 1, st)) return rc;
-    if (dW) (void)hipMemcpyAsync(dW, red, sizeof(float) * n, hipMemcpyDeviceToDevice, st);
-    if (dbias) (void)hipMemcpyAsync(dbias, red + n, sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (int rc = slab_reduce(slab, red, grid, n + 1, wst)) return rc;
+    if (dW) (void)hipMemcpyAsync(dW, red, sizeof(float) * n, hipMemcpyDeviceToDevice, wst);
+    if (dbias) (void)hipMemcpyAsync(dbias, red + n, sizeof(float), hipMemcpyDeviceToDevice, wst);
   }
   if (dX) {
     const int grid = c1_grid(p, 1024);

@@ -6,6 +6,10 @@
 // rdst_reduce_batch_begin() and rdst_reduce_batch_end() the ops RECORD their reductions instead of launching them and
 // _end() runs all of them as two launches (every sum, then every LayerNorm finish): a Swin block's backward needs 2
 // instead of 6.  The slabs and the G scratch must stay alive until _end() returns (they are the ops' workspaces).
+//
+// Nothing later on the backward chain reads what these two launches write, so with rdst_side_enable(1) _end() issues them on a
+// side stream, forked from and rejoined to the caller's stream by events (include/rdst_hip.h, "the side branch"): they run
+// beside the next layer's backward instead of in front of it.  The slabs then have to outlive the NEXT _end() (or a join).
 #pragma once
 #include "common.h"
 
@@ -39,3 +43,17 @@ struct FinJob {                            // dW = s (gamma G + beta db), dbias 
 int sum(const SumJob& j, hipStream_t st);
 int finish(const FinJob& j, hipStream_t st);
 }  // namespace rbatch
+
+// The side branch for ONE launch site outside a reduction batch (a conv's weight gradient beside its data gradient):
+//   rside::Fork f;  fork_begin(st, f);  launch on f.run;  fork_end(f);
+// f.run is the side stream, ordered behind everything issued on `st` so far, when the branch's bit `RDST_SIDE_CONV` is on and
+// its resources exist (like rdst_reduce_batch_end it creates them outside stream capture only); otherwise f.run == st and
+// fork_end does nothing.
+// What the launches read has to stay alive as for a generation of reductions; what they write is complete after the next
+// rdst_reduce_batch_end() on `st` or rdst_side_join(st).
+namespace rside {
+constexpr int SIDE_REDUCE = 1, SIDE_CONV = 2;   // bits of rdst_side_enable()'s argument
+struct Fork { hipStream_t run = nullptr; void* dev = nullptr; unsigned long long cap = 0; };
+int fork_begin(hipStream_t st, Fork& f);
+int fork_end(Fork& f);
+}  // namespace rside

@@ -1,5 +1,7 @@
 // See reduce_batch.h.
 #include "reduce_batch.h"
+#include <atomic>
+#include <mutex>
 #include <vector>
 
 namespace rbatch {
@@ -185,6 +187,162 @@ int finish(const FinJob& j, hipStream_t st) {
 
 }  // namespace rbatch
 
+// ------------------------------------------------------------------------------------------------
+// The side branch (reduce_batch.h): one non-blocking stream per device on which rdst_reduce_batch_end() runs its two
+// launches while the caller's stream goes on with the backward chain.  Ordering is by events alone.
+// ------------------------------------------------------------------------------------------------
+namespace rside {
+
+constexpr int MAXDEV = 16;
+constexpr int RING = 4;   // a generation takes two events (fork, close); a wait holds the record it was issued on, so two generations suffice
+constexpr unsigned long long NO_CAPTURE = 0;
+
+struct Dev {
+  hipStream_t side = nullptr;
+  hipEvent_t ev[RING] = {};
+  bool ready = false;
+  int next = 0;                       // ring slot of the next generation's fork event (its close event is next + 1)
+  int pending = -1;                   // ring slot of the close event nobody waits for yet; -1: no generation pending
+  unsigned long long pending_cap = NO_CAPTURE;   // id of the stream capture that event was recorded in (NO_CAPTURE: eagerly)
+};
+
+std::atomic<int> g_enabled{0};       // process-wide: set on the Python thread, read on autograd's device thread
+std::mutex g_mu;                     // guards g_dev
+Dev g_dev[MAXDEV];
+
+int hip_fail(hipError_t e, const char* what) { return rdst_fail(-(int)e, "%s: %s", what, hipGetErrorString(e)); }
+
+// the device `st` runs on, and the id of the capture it is part of (NO_CAPTURE outside one)
+int where(hipStream_t st, int& dev, unsigned long long& cap) {
+  hipError_t e = st ? hipStreamGetDevice(st, &dev) : hipGetDevice(&dev);
+  if (e != hipSuccess) return hip_fail(e, "rdst_side: device of the stream");
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  unsigned long long id = 0;
+  e = hipStreamGetCaptureInfo(st, &cs, &id);
+  if (e != hipSuccess) return hip_fail(e, "rdst_side: hipStreamGetCaptureInfo");
+  if (cs == hipStreamCaptureStatusInvalidated) return rdst_fail(RDST_EINVAL, "rdst_side: the stream's capture is invalidated");
+  // (ids start at 1; the + 1 keeps NO_CAPTURE distinct whatever the runtime hands out)
+  cap = cs == hipStreamCaptureStatusActive ? id + 1 : NO_CAPTURE;
+  return 0;
+}
+
+int create(Dev& d, int dev) {
+  int cur = -1;
+  hipError_t e = hipGetDevice(&cur);
+  if (e == hipSuccess && cur != dev) e = hipSetDevice(dev);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&d.side, hipStreamNonBlocking);
+  for (int k = 0; k < RING && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&d.ev[k], hipEventDisableTiming);
+  if (cur >= 0 && cur != dev) (void)hipSetDevice(cur);
+  if (e != hipSuccess) {
+    for (int k = 0; k < RING; ++k)
+      if (d.ev[k]) { (void)hipEventDestroy(d.ev[k]); d.ev[k] = nullptr; }
+    if (d.side) { (void)hipStreamDestroy(d.side); d.side = nullptr; }
+    return hip_fail(e, "rdst_side: creating the side stream");
+  }
+  d.ready = true;
+  d.next = 0;
+  d.pending = -1;
+  return 0;
+}
+
+// `st` waits for the pending generation, if it can: a generation recorded in a capture that is over (it failed, or it
+// was left without a join and so could not be instantiated) is forgotten; an eager one cannot be waited for from inside
+// a capture (that dependency would not be part of the graph): the caller has to join first.
+int wait_pending(Dev& d, hipStream_t st, unsigned long long cap, const char* who) {
+  if (d.pending < 0) return 0;
+  if (d.pending_cap == cap) {
+    hipError_t e = hipStreamWaitEvent(st, d.ev[d.pending], 0);
+    if (e != hipSuccess) return hip_fail(e, who);
+  } else if (d.pending_cap == NO_CAPTURE) {
+    return rdst_fail(RDST_EINVAL, "%s: side work issued before this stream capture began is still pending (rdst_side_join first)", who);
+  }
+  d.pending = -1;
+  return 0;
+}
+
+// steps (a) and (b); a single launch site (fork_begin: `reductions` false) takes (b) alone.  d stays null where the serial
+// path has to be taken: nothing created yet and `st` is capturing, or a device index beyond the table.
+int open_generation(hipStream_t st, Dev*& d, unsigned long long& cap, bool reductions = true) {
+  int dev = 0;
+  if (int rc = where(st, dev, cap)) return rc;
+  if (dev < 0 || dev >= MAXDEV) return 0;
+  Dev& D = g_dev[dev];
+  if (!D.ready) {
+    if (cap != NO_CAPTURE) return 0;   // never create a stream or an event while capturing
+    if (int rc = create(D, dev)) return rc;
+  }
+  if (reductions) {
+    if (int rc = wait_pending(D, st, cap, "rdst_reduce_batch_end")) return rc;
+  } else if (D.pending >= 0 && D.pending_cap != cap) {
+    // a single launch site does not wait for the generation before it (its own closing event will stand for both: the side
+    // stream runs in order) - but that generation must belong to the same capture, or to none, as `st`
+    if (D.pending_cap == NO_CAPTURE) return rdst_fail(RDST_EINVAL, "rdst_side: side work issued before this stream capture began is still pending");
+    D.pending = -1;
+  }
+  hipError_t e = hipEventRecord(D.ev[D.next], st);
+  if (e == hipSuccess) e = hipStreamWaitEvent(D.side, D.ev[D.next], 0);
+  if (e != hipSuccess) return hip_fail(e, "rdst_reduce_batch_end: forking the side stream");
+  d = &D;
+  return 0;
+}
+
+// step (a) alone
+int wait_only(hipStream_t st) {
+  int dev = 0;
+  unsigned long long cap = 0;
+  if (int rc = where(st, dev, cap)) return rc;
+  if (dev < 0 || dev >= MAXDEV || !g_dev[dev].ready) return 0;
+  return wait_pending(g_dev[dev], st, cap, "rdst_reduce_batch_end");
+}
+
+// step (d)
+int close_generation(Dev& d, unsigned long long cap) {
+  const int slot = d.next + 1;
+  hipError_t e = hipEventRecord(d.ev[slot], d.side);
+  if (e != hipSuccess) return hip_fail(e, "rdst_reduce_batch_end: closing the side generation");
+  d.pending = slot;
+  d.pending_cap = cap;
+  d.next = (d.next + 2) % RING;
+  return 0;
+}
+
+// Forget every pending generation.  One that was issued eagerly may still be running and nothing will wait for it any
+// more, so the host waits here (an error path); one recorded in a capture never ran.  Without a device nothing was ever
+// created and no HIP call is made.
+int forget_all(const char* who) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = 0;
+  for (Dev& d : g_dev) {
+    if (!d.ready || d.pending < 0) continue;
+    if (d.pending_cap == NO_CAPTURE) {
+      hipError_t e = hipStreamSynchronize(d.side);
+      if (e != hipSuccess && !rc) rc = hip_fail(e, who);
+    }
+    d.pending = -1;
+  }
+  return rc;
+}
+
+int fork_begin(hipStream_t st, Fork& f) {
+  f.run = st;
+  f.dev = nullptr;
+  if (!(g_enabled.load(std::memory_order_relaxed) & SIDE_CONV)) return 0;
+  std::lock_guard<std::mutex> lk(g_mu);
+  Dev* d = nullptr;
+  if (int rc = open_generation(st, d, f.cap, false)) return rc;
+  if (d) { f.dev = d; f.run = d->side; }
+  return 0;
+}
+int fork_end(Fork& f) {
+  if (!f.dev) return 0;
+  std::lock_guard<std::mutex> lk(g_mu);
+  Dev* d = static_cast<Dev*>(f.dev);
+  f.dev = nullptr;
+  return close_generation(*d, f.cap);
+}
+
+}  // namespace rside
+
 extern "C" int rdst_reduce_batch_begin(void) {
   if (rbatch::g_active) return rdst_fail(RDST_EINVAL, "rdst_reduce_batch_begin: a batch is already open on this thread");
   rbatch::g_active = true;
@@ -197,8 +355,26 @@ extern "C" int rdst_reduce_batch_end(void* stream) {
   if (!rbatch::g_active) return rdst_fail(RDST_EINVAL, "rdst_reduce_batch_end: no open batch");
   rbatch::g_active = false;
   hipStream_t st = (hipStream_t)stream;
-  int rc = rbatch::launch_sums(rbatch::g_sums.data(), (int)rbatch::g_sums.size(), st);
-  if (!rc) rc = rbatch::launch_fins(rbatch::g_fins.data(), (int)rbatch::g_fins.size(), st);
+  int rc = 0;
+  if (const int bits = rside::g_enabled.load(std::memory_order_relaxed)) {
+    // the side branch: (a) `st` behind the previous generation, (b) the side stream behind `st`, (c) the same two launches
+    // there, (d) the generation's closing event.  A generation that was opened is always closed, so a join finds its end.
+    // With the conv stage alone, (a) is all that happens: the launches stay on `st`, behind the weight gradients issued so far.
+    std::lock_guard<std::mutex> lk(rside::g_mu);
+    rside::Dev* d = nullptr;
+    unsigned long long cap = 0;
+    rc = (bits & rside::SIDE_REDUCE) ? rside::open_generation(st, d, cap) : rside::wait_only(st);
+    hipStream_t run = d ? d->side : st;
+    if (!rc) rc = rbatch::launch_sums(rbatch::g_sums.data(), (int)rbatch::g_sums.size(), run);
+    if (!rc) rc = rbatch::launch_fins(rbatch::g_fins.data(), (int)rbatch::g_fins.size(), run);
+    if (d) {
+      const int rc2 = rside::close_generation(*d, cap);
+      if (!rc) rc = rc2;
+    }
+  } else {
+    rc = rbatch::launch_sums(rbatch::g_sums.data(), (int)rbatch::g_sums.size(), st);
+    if (!rc) rc = rbatch::launch_fins(rbatch::g_fins.data(), (int)rbatch::g_fins.size(), st);
+  }
   rbatch::g_sums.clear();
   rbatch::g_fins.clear();
   return rc;
@@ -209,5 +385,19 @@ extern "C" int rdst_reduce_batch_abort(void) {
   rbatch::g_active = false;
   rbatch::g_sums.clear();
   rbatch::g_fins.clear();
-  return 0;
+  return rside::forget_all("rdst_reduce_batch_abort");   // (the side work already issued wrote into the same dead pass)
 }
+
+extern "C" int rdst_side_enable(int on) { return rside::g_enabled.exchange(on & (rside::SIDE_REDUCE | rside::SIDE_CONV)); }
+
+extern "C" int rdst_side_join(void* stream) {
+  std::lock_guard<std::mutex> lk(rside::g_mu);
+  hipStream_t st = (hipStream_t)stream;
+  int dev = 0;
+  unsigned long long cap = 0;
+  if (int rc = rside::where(st, dev, cap)) return rc;
+  if (dev < 0 || dev >= rside::MAXDEV || !rside::g_dev[dev].ready) return 0;
+  return rside::wait_pending(rside::g_dev[dev], st, cap, "rdst_side_join");
+}
+
+extern "C" int rdst_side_reset(void) { return rside::forget_all("rdst_side_reset"); }

@@ -18,7 +18,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _lib, side
 from ._lib import ACT_GELU, ACT_LEAKY001, ACT_LEAKY02, ACT_NONE, BF16, F32, F32X3  # noqa: F401
 
 
@@ -606,13 +606,25 @@ class _ReduceBatchState(threading.local):
             self.abandon(lib)
             self.epoch = type(self).EPOCH
 
-    def _flush(self, lib):
-        """Run what is queued; the workspaces and scratch destinations it read are released whether it worked or not."""
+    def _flush(self, lib, join=False):
+        """Run what is queued; the workspaces and scratch destinations it read are released whether it worked or not.
+        With the side branch on (rdst_amd.side: the trainer's backward) the reductions are only ISSUED here, beside the
+        chain: what they read is parked for one more flush, and what they write is complete after side.join() - at once
+        where autograd may read it when the node returns (`join`: fresh destinations, a foreign pass; or no
+        detach_grads() bracket is open, so nobody else will join), else when the trainer joins after the pass."""
+        on_side = side.enabled()
         try:
             _lib.check(lib.rdst_reduce_batch_end(_stream()), "rdst_reduce_batch_end")
         finally:
+            if on_side:
+                side.park(self.keep)
             self.keep = []
             self.fresh = 0
+        if on_side:
+            from . import dp
+            side.release_older()   # the call above has ordered this stream behind the generation parked before
+            if join or not dp._OFFERED:
+                side.join()
 
     def begin(self, lib):
         self._drop_stale(lib)
@@ -647,7 +659,7 @@ class _ReduceBatchState(threading.local):
         gradient destination that autograd may read on return, run what is queued now (and keep the batch open)."""
         self._drop_stale(lib)
         if self.depth > 0 and (self.fresh or self._foreign()):
-            self._flush(lib)
+            self._flush(lib, join=True)
             _lib.check(lib.rdst_reduce_batch_begin(), "rdst_reduce_batch_begin")
         elif self.depth == 0:
             self.fresh = 0
@@ -669,10 +681,11 @@ _ReduceBatch = _ReduceBatchState()
 def reset_backward_state() -> None:
     """After a backward pass that did not run to its end (an exception inside a node, a failed HIP-graph capture): every
     thread drops the reduction batch it still holds open - its queued jobs name workspaces of the dead pass - the next
-    time it touches one.  The calling thread's is dropped at once."""
+    time it touches one.  The calling thread's is dropped at once, and so is the side branch's state (rdst_amd.side)."""
     type(_ReduceBatch).EPOCH += 1
     if _lib.loaded():
         _ReduceBatch._drop_stale(_lib.load())
+    side.reset()   # no side generation stays pending, none parked
 
 
 class GradSink:
@@ -1006,9 +1019,17 @@ class _ConvRows(torch.autograd.Function):
         db = _bias_grad(ctx, need[2])
         nbytes = lib.rdst_conv_bwd_workspace(B, H, W, Cin, Cout, k)
         wsp = _workspace(nbytes, dev)
+        # (side branch, stage 2: with both gradients wanted the library runs the weight gradient beside the data gradient)
+        forked = side.conv_enabled() and dx is not None and (dw is not None or db is not None)
+        fresh = _ReduceBatch.fresh
         _lib.check(lib.rdst_conv_bwd(x.data_ptr(), ldx, in_act, w.data_ptr(), dy_r.data_ptr(), lddy, _ptr(dx), Cin,
                                      None, 0, _ptr(dw), _ptr(db), wsp.data_ptr(), nbytes, B, H, W, Cin, Cout, k,
                                      out_scale, r, code, _stream()), "rdst_conv_bwd")
+        if forked:
+            from . import dp
+            side.park_current([x, dy_r, wsp])   # what the weight gradient reads; released one flush later
+            if fresh or not dp._OFFERED:         # autograd may read dw / db when this node returns
+                side.join()
         _ReduceBatch.settle(lib)   # (a conv inside an open outer batch: nothing of its own is deferred, its fresh destinations settle)
         dres = dy if (has_res and need[3]) else None
         return dx, dw, db, dres, None, None, None, None

@@ -29,7 +29,7 @@ import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 
-from . import dp
+from . import dp, side
 from .optim import FlatAdam
 
 GUARD_OFF = 1e8   # config_files/RDST_E1_OASIS_example_SRx4.ini:136
@@ -180,7 +180,17 @@ class DPTrainStep:
         # 17.6 -> 20.0 ms/step.  The ~1.7 GB of slabs then stay allocated until the end of the pass; per DenseSTLayer they are
         # 22-30 MB buffers that the caching allocator hands out again and again, written and summed while still in the 256 MiB
         # Infinity Cache.)
-        loss.backward()
+        # The layers' slab sums and LayerNorm finishes, and the convs' weight gradients, feed nothing before the optimizer: they
+        # run on a side stream beside the dX chain (rdst_amd.side; RDST_SIDE_BRANCH=0 / RDST_SIDE_CONV=0 keep them on it).  The
+        # join orders this stream behind them before the bucket is touched, and inside a capture it is what rejoins the branch.
+        side.enable()
+        try:
+            loss.backward()
+        finally:
+            try:
+                side.join()
+            finally:
+                side.disable()
         self.bucket.gather()             # whatever was not written in place is flattened into the bucket
         return self._loss_buf
 
