@@ -502,6 +502,22 @@ int rdst_unfold_tiles(const float* x, float* out, int N, int C, int H, int W, in
  * No atomics: the same bits on every run. */
 int rdst_fold_tiles(const float* tiles, float* out, int N, int C, int H, int W, int P, int S, int pad_y, int pad_x, int Ly,
                     int Lx, void* stream);
+/* The x8 geometric self-ensemble (SRTester(self_ensemble=True)): the eight flips / transposes of a square tile are numbered
+ * k = 0..7, T_k(x)[i][j] = x[a][b] with (a, b) = (j, i) if k & 4, else (i, j); then a = p - 1 - a if k & 2 and
+ * b = p - 1 - b if k & 1 (tiling.dihedral: flip the columns, flip the rows, then transpose).
+ *
+ * Unfold: the plain unfold with every tile written eight times.  out fp32 (n_slots, C, p, p), contiguous: slot j holds
+ * T_(j % 8) of tile first_tile + j / 8, the pad rule applied to the tile before the transform; the slots of tiles past the
+ * last are zeros.  n_slots must be a positive multiple of 8; plan checks, limits and refusals as for the plain unfold.
+ * Every source pixel of a tile is read once (into LDS) and written eight times. */
+int rdst_unfold_tiles_d8(const float* x, float* out, int N, int C, int H, int W, int p, int s, int pad_y, int pad_x, int Ly,
+                         int Lx, int pad_mode, int64_t first_tile, int n_slots, void* stream);
+/* Merge: y fp32 (8 * n_tiles, C, P, P) -> out fp32 (n_tiles, C, P, P), both contiguous:
+ *   out[t] = (((T_0^-1(y[8 t]) + T_1^-1(y[8 t + 1])) + ... ) + T_7^-1(y[8 t + 7])) * 0.125f
+ * in fp32, k ascending, strictly left to right; T_k^-1 undoes the three steps of T_k in the opposite order (NOT T_k itself
+ * for k = 5, 6).  Every output pixel is summed by one thread, no atomics: the same bits on every run.  Non-positive sizes,
+ * null pointers and sizes past the limits of the fold are refused (RDST_EINVAL). */
+int rdst_merge_tiles_d8(const float* y, float* out, int n_tiles, int C, int P, void* stream);
 
 /* ---- Device-side step guard (rdst_amd/optim.py FlatAdam(device_state=True), rdst_amd/trainer.py device_guard) ------------
  * The update guard of the reference's inner loop, models/trans_sr_trainer.py:162-174

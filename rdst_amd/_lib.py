@@ -102,6 +102,8 @@ SIGNATURES = {
     # tiled whole-slice inference (rdst_amd.tiling)
     "rdst_unfold_tiles": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _l, _i, _p]),
     "rdst_fold_tiles": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "rdst_unfold_tiles_d8": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _l, _i, _p]),
+    "rdst_merge_tiles_d8": (_i, [_p, _p, _i, _i, _i, _p]),
     # the device-side step guard (rdst_amd.optim.FlatAdam(device_state=True))
     "rdst_step_guard_workspace": (_z, [_l]),
     "rdst_step_guard": (_i, [_p, C.c_double, _p, _p, _l, C.c_double, _i, _p, _z, _p, _p]),

@@ -46,12 +46,18 @@ class SRTester:
     weights is a node of the captured forward, so the graph reads the live parameters: ``load_state_dict`` between calls needs
     no recapture.  The graph is dropped, and captured again on the next full batch, when the parameters move or change dtype or
     the compute mode changes (``PackPlan.valid``).  A failed capture warns and the tester runs eagerly from then on.
-    ``graph_captures`` / ``graph_replays`` count what happened."""
+    ``graph_captures`` / ``graph_replays`` count what happened.
+
+    ``self_ensemble=True`` (the tiled path only; ``tile_batch`` a multiple of 8): the x8 geometric self-ensemble, the "+" of
+    EDSR / RCAN / SwinIR, per tile.  A network call carries ``tile_batch / 8`` tiles, each under its eight flips and
+    transposes (``tiling.unfold_tiles_d8``, slot ``8 t + k``); the eight outputs are transformed back and averaged in fp32
+    (``tiling.merge_tiles_d8``) straight into the tile buffer, which is folded as before.  Tiles are square, so the tile batch
+    and the captured graph are the ones of the plain path: 8x the network calls, one unfold and one merge launch per call."""
 
     def __init__(self, net: torch.nn.Module, batch_size: int = 16, sr_scale: Optional[float] = None,
                  metrics: str = "psnr ssim", compute_dtype: Optional[torch.dtype] = None, *, tile: Optional[int] = None,
                  tile_stride: Optional[int] = None, tile_batch: int = 32, pad_mode: str = "zero", graph: bool = False,
-                 tile_buffer_bytes: int = 1 << 30):
+                 tile_buffer_bytes: int = 1 << 30, self_ensemble: bool = False):
         self.net = net
         self.batch_size = int(batch_size)
         self.sr_scale = float(sr_scale if sr_scale is not None else getattr(net, "sr_scale", getattr(net, "upscale", 1)))
@@ -64,6 +70,10 @@ class SRTester:
         self.tile_stride = self.tile if tile_stride is None else int(tile_stride)
         self.tile_batch, self.pad_mode, self.tile_buffer_bytes = int(tile_batch), pad_mode, int(tile_buffer_bytes)
         self.use_graph = bool(graph) and self.tile is not None
+        self.self_ensemble = bool(self_ensemble)
+        if self.self_ensemble and self.tile is None:
+            raise ValueError("SRTester: self_ensemble=True needs the tiled path (tile=...); a square slice that is a multiple of "
+                             "the window size can be run as one tile (tile=H, tile_stride=H)")
         self.graph = None
         self.graph_captures = self.graph_replays = 0
         self._static_in = self._static_out = self._graph_plan = self._graph_sig = None
@@ -83,6 +93,9 @@ class SRTester:
                 raise ValueError(f"SRTester: pad_mode must be one of {sorted(PAD_MODES)}, got {pad_mode!r}")
             if self.sr_scale != int(self.sr_scale) or self.sr_scale < 1:
                 raise ValueError(f"SRTester: the tiled path needs an integer scale, got {self.sr_scale}")
+            if self.self_ensemble and self.tile_batch % 8:
+                raise ValueError(f"SRTester: self_ensemble=True fills a network call with the eight variants of whole tiles; "
+                                 f"tile_batch={self.tile_batch} must be a multiple of 8")
 
     @torch.no_grad()
     def inference(self, lr_img: torch.Tensor) -> torch.Tensor:
@@ -104,12 +117,14 @@ class SRTester:
 
     def _tiled(self, lr_img: torch.Tensor, dev) -> torch.Tensor:
         from . import ops
-        from .tiling import fold_tiles
+        from .tiling import fold_tiles, merge_tiles_d8
         if lr_img.dim() != 4 or min(lr_img.shape) <= 0:
             raise ValueError(f"SRTester.inference: lr_img must be a non-empty (N, C, h, w), got {tuple(lr_img.shape)}")
         N, C, h, w = lr_img.shape
         plan = self._tile_plan(h, w)
-        T, P, B = plan.tiles_per_slice, plan.hr.patch, self.tile_batch
+        T, P = plan.tiles_per_slice, plan.hr.patch
+        E = 8 if self.self_ensemble else 1              # network inputs per tile
+        B = self.tile_batch // E                        # tiles per network call
         per_chunk = max(1, self.tile_buffer_bytes // (T * C * P * P * 4))
         rec = []
         with torch.cuda.device(dev), ops.keep_pack_plan(self.net):
@@ -130,16 +145,23 @@ class SRTester:
                         if tuple(y.shape[1:]) != (C, P, P):
                             raise RuntimeError(f"SRTester.inference: the network maps a {(C, self.tile, self.tile)} tile to "
                                                f"{tuple(y.shape[1:])}, the plan expects {(C, P, P)}")
-                        tiles[f:f + m].copy_(y[:m])
+                        if self.self_ensemble:
+                            merge_tiles_d8(y[:E * m] if y.dtype == torch.float32 else y[:E * m].float(), out=tiles[f:f + m])
+                        else:
+                            tiles[f:f + m].copy_(y[:m])
                     rec.append(fold_tiles(tiles, plan, n))
             finally:
                 self._plan = ops.pack_plan_of(self.net)
         return rec[0] if len(rec) == 1 else torch.cat(rec, dim=0)
 
     def _forward_tiles(self, x: torch.Tensor, plan, first: int, m: int) -> torch.Tensor:
-        """The SR tiles of tiles ``[first, first + m)`` of ``x``: at least ``m`` rows, the network's output or the graph's."""
-        from .tiling import unfold_tiles
-        B, C = self.tile_batch, x.shape[1]
+        """The SR tiles of tiles ``[first, first + m)`` of ``x``: at least ``m`` rows (``8 m`` with the self-ensemble, row
+        ``8 t + k`` for variant ``k`` of tile ``first + t``), the network's output or the graph's."""
+        from .tiling import unfold_tiles, unfold_tiles_d8
+        C = x.shape[1]
+        if self.self_ensemble:
+            unfold_tiles, m = unfold_tiles_d8, 8 * m    # m network inputs, eight per tile
+        B = self.tile_batch
         if self.use_graph and self.graph is None and m == B and self._eager_full >= 1:
             self._capture(C, x.device)
         if self.graph is not None and tuple(self._static_in.shape[1:2]) == (C,) and self._static_in.device == x.device:

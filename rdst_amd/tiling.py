@@ -25,8 +25,15 @@ uncovered (only some ``n < p`` do) raises ``ValueError``.
 ``ImageFolder``: when ``p - margin`` is odd its HR padding is ``ceil(scale (p - margin) / 2)``, not ``scale ceil((p - margin) /
 2)``, and its SR tiles are folded up to ``scale / 2`` pixels away from where their LR tiles were cut.  Non-integer scales raise.
 
+**The x8 geometric self-ensemble** (``SRTester(self_ensemble=True)``): ``dihedral(x, k)`` / ``dihedral_inverse(y, k)``, k in
+0..7, are the eight flips and transposes of the last two dims and their inverses (torch views, any device: the semantics and
+the tests' oracle).  ``unfold_tiles_d8`` is ``unfold_tiles`` with every tile written eight times, slot ``8 t + k`` holding
+``dihedral(tile t, k)``; ``merge_tiles_d8`` maps the network's outputs ``y (8 n, C, P, P)`` to ``(n, C, P, P)``,
+``((((y0' + y1') + y2') + ...) + y7') * 0.125`` with ``yk' = dihedral_inverse(y[8 t + k], k)``, in fp32, k ascending.  One launch
+each (rdst_unfold_tiles_d8 / rdst_merge_tiles_d8); the merged tiles are folded by ``fold_tiles`` as they are.
+
 ``pad_mode='zero'`` pads the LR slice with zeros, as ``nn.Unfold(padding=...)`` and the reference do; ``'edge'`` repeats the
-edge, as ``data.edge_pad`` does.  Both functions run on GPU tensors only; there is no CPU path."""
+edge, as ``data.edge_pad`` does.  The unfold, fold and merge functions run on GPU tensors only; there is no CPU path."""
 from __future__ import annotations
 
 from typing import NamedTuple, Optional
@@ -99,6 +106,35 @@ class TilePlan:
         return f"TilePlan(lr={self.lr}, scale={self.scale}, pad_mode={self.pad_mode!r})"
 
 
+def dihedral(x: torch.Tensor, k: int) -> torch.Tensor:
+    """Transform ``k`` (0..7) of the last two dims, a view: flip the columns if ``k & 1``, flip the rows if ``k & 2``, then
+    transpose if ``k & 4``.  On a ``p x p`` image ``dihedral(x, k)[i, j] = x[a, b]`` with ``(a, b) = (j, i) if k & 4 else (i, j)``,
+    then ``a = p - 1 - a if k & 2`` and ``b = p - 1 - b if k & 1``."""
+    if not 0 <= int(k) < 8:
+        raise ValueError(f"dihedral: k must be in 0..7, got {k}")
+    if k & 1:
+        x = x.flip(-1)
+    if k & 2:
+        x = x.flip(-2)
+    if k & 4:
+        x = x.transpose(-1, -2)
+    return x
+
+
+def dihedral_inverse(y: torch.Tensor, k: int) -> torch.Tensor:
+    """Undo ``dihedral(., k)``: the same three steps in the opposite order (``dihedral`` itself is NOT its inverse for
+    ``k`` = 5 and 6, a flip of one axis followed by the transpose)."""
+    if not 0 <= int(k) < 8:
+        raise ValueError(f"dihedral_inverse: k must be in 0..7, got {k}")
+    if k & 4:
+        y = y.transpose(-1, -2)
+    if k & 2:
+        y = y.flip(-2)
+    if k & 1:
+        y = y.flip(-1)
+    return y
+
+
 def _need_gpu(what: str, *ts: torch.Tensor) -> None:
     for t in ts:
         if not isinstance(t, torch.Tensor):
@@ -160,4 +196,60 @@ def fold_tiles(tiles: torch.Tensor, plan: TilePlan, N: int) -> torch.Tensor:
         out = torch.empty(N, C, g.H, g.W, dtype=torch.float32, device=tiles.device)
         _lib.check(_lib.load().rdst_fold_tiles(tiles.data_ptr(), out.data_ptr(), N, C, g.H, g.W, g.patch, g.stride, g.pad_y,
                                                g.pad_x, g.Ly, g.Lx, _stream()), "rdst_fold_tiles")
+    return out
+
+
+def unfold_tiles_d8(x: torch.Tensor, plan: TilePlan, out: Optional[torch.Tensor] = None, first_tile: int = 0,
+                    n_slots: Optional[int] = None) -> torch.Tensor:
+    """``unfold_tiles`` with every tile written eight times: slot ``j`` of the contiguous ``(n_slots, C, p, p)`` result holds
+    ``dihedral(tile first_tile + j // 8, j % 8)``, the pad rule applied before the transform.  ``n_slots`` (a multiple of 8)
+    defaults to 8 times the tiles from ``first_tile`` to the last (the shape of ``out`` when that is given); the slots of tiles
+    past the last are zeros."""
+    _need_gpu("unfold_tiles_d8", x)
+    g = plan.lr
+    if x.dim() != 4 or tuple(x.shape[-2:]) != (g.H, g.W) or x.shape[0] <= 0 or x.shape[1] <= 0:
+        raise ValueError(f"unfold_tiles_d8: x must be (N, C, {g.H}, {g.W}), got {tuple(x.shape)}")
+    N, C = int(x.shape[0]), int(x.shape[1])
+    first_tile = int(first_tile)
+    if n_slots is None:
+        n_slots = int(out.shape[0]) if out is not None else 8 * (N * plan.tiles_per_slice - first_tile)
+    n_slots = int(n_slots)
+    if first_tile < 0 or n_slots <= 0:
+        raise ValueError(f"unfold_tiles_d8: first_tile={first_tile} n_slots={n_slots} select no tile of "
+                         f"{N * plan.tiles_per_slice}")
+    if n_slots % 8:
+        raise ValueError(f"unfold_tiles_d8: n_slots={n_slots} must be a multiple of 8 (eight slots per tile)")
+    shape = (n_slots, C, g.patch, g.patch)
+    x = x.contiguous()
+    with torch.cuda.device(x.device):
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=x.device)
+        else:
+            _need_gpu("unfold_tiles_d8", out)
+            if tuple(out.shape) != shape or out.device != x.device or not out.is_contiguous():
+                raise ValueError(f"unfold_tiles_d8: out must be a contiguous float32 {shape} tensor on {x.device}")
+        _lib.check(_lib.load().rdst_unfold_tiles_d8(x.data_ptr(), out.data_ptr(), N, C, g.H, g.W, g.patch, g.stride, g.pad_y,
+                                                    g.pad_x, g.Ly, g.Lx, PAD_MODES[plan.pad_mode], first_tile, n_slots,
+                                                    _stream()), "rdst_unfold_tiles_d8")
+    return out
+
+
+def merge_tiles_d8(y: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 CUDA ``y (8 n, C, P, P)``, slot ``8 t + k`` the network's output for ``dihedral(tile t, k)`` -> ``(n, C, P, P)``
+    (``out``, e.g. a run of rows of a larger tile buffer, or a new tensor): the fp32 sum of ``dihedral_inverse(y[8 t + k], k)``
+    over ascending ``k``, left to right, times 0.125.  Deterministic: the same ``y`` gives the same bits."""
+    _need_gpu("merge_tiles_d8", y)
+    if y.dim() != 4 or y.shape[0] <= 0 or y.shape[0] % 8 or y.shape[1] <= 0 or y.shape[2] != y.shape[3] or y.shape[2] <= 0:
+        raise ValueError(f"merge_tiles_d8: y must be (8 n, C, P, P), got {tuple(y.shape)}")
+    n, C, P = int(y.shape[0]) // 8, int(y.shape[1]), int(y.shape[2])
+    shape = (n, C, P, P)
+    y = y.contiguous()
+    with torch.cuda.device(y.device):
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=y.device)
+        else:
+            _need_gpu("merge_tiles_d8", out)
+            if tuple(out.shape) != shape or out.device != y.device or not out.is_contiguous():
+                raise ValueError(f"merge_tiles_d8: out must be a contiguous float32 {shape} tensor on {y.device}")
+        _lib.check(_lib.load().rdst_merge_tiles_d8(y.data_ptr(), out.data_ptr(), n, C, P, _stream()), "rdst_merge_tiles_d8")
     return out

@@ -121,7 +121,30 @@ def w16(D, tabf):
     ]
 
 
+def d8_blocks():
+    """rdst_amd/csrc/tiles.hip: unfold_d8_kernel / merge_d8_kernel, the 32 x 32 block with rows of 33 floats.  V = 1: thread =
+    (r = tid / 32, c = tid % 32); V = 4: (r = tid / 8, q = tid % 8), four b32 accesses e = 0..3 of the columns 4 q + e.  Row
+    accesses touch [r][c], the transposed variants [c][r]."""
+    LD = 33
+    rows = []
+    for e in (0, 3):
+        rows += [
+            (f"V=4 row access [r][4q+{e}]", "read_b32", lambda l, e=e: 4 * ((l >> 3) * LD + 4 * (l & 7) + e), "stage writes alike"),
+            (f"V=4 column read [4q+{e}][r]", "read_b32", lambda l, e=e: 4 * ((4 * (l & 7) + e) * LD + (l >> 3)), "4 per variant"),
+        ]
+    rows += [
+        ("V=1 row access [r][c]", "read_b32", lambda l: 4 * ((l >> 5) * LD + (l & 31)), ""),
+        ("V=1 column read [c][r]", "read_b32", lambda l: 4 * ((l & 31) * LD + (l >> 5)), ""),
+        ("V=4 stage write [r][4q+1]", "write_b32", lambda l: 4 * ((l >> 3) * LD + 4 * (l & 7) + 1), ""),
+        ("V=1 stage write [r][c]", "write_b32", lambda l: 4 * ((l >> 5) * LD + (l & 31)), ""),
+        ("(unpadded rows of 32: column read)", "read_b32", lambda l: 4 * ((l & 31) * 32 + (l >> 5)), "what the pad avoids"),
+    ]
+    return rows
+
+
 if __name__ == "__main__":
+    print("== tiles.hip d8 blocks (rows of 33 floats)")
+    report(d8_blocks())
     for nct in (2, 3, 4):
         print(f"== mlp_bwd_kernel<{nct}> (C = {30 * nct})")
         report(mlp_bwd(nct))
