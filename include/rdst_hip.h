@@ -482,6 +482,18 @@ int rdst_resize_bicubic(const float* x, float* y, int N, int C, int H, int W, in
 int rdst_sample_patches(const float* stack, const uint8_t* labels, const int32_t* index, float* hr, float* lr,
                         uint8_t* label_out, int S, int C, int H, int W, int B, int hp, int lp, const int32_t* tap_index,
                         const float* tap_weight, void* stream);
+/* The sampler with the flips and transposes of training augmentation: patch b is cut as above, then turned by T_k with
+ * k = variant[b] & 7 (the numbering of the x8 self-ensemble below: T_k(x)[i][j] = x[a][b], (a, b) = (j, i) if k & 4 else
+ * (i, j), then a = hp - 1 - a if k & 2, b = hp - 1 - b if k & 1), then degraded: hr[b] = T_k(window b), label_out[b] =
+ * T_k(label window b), and lr[b] is the resize of the TURNED patch, by the same chains of taps in the ascending order of its
+ * rows and columns, so lr equals rdst_resize_bicubic of hr bit for bit (resizing first and turning afterwards would not: the
+ * chain is not flip invariant in fp32).  `variant` is DEVICE memory of B int32 the host never reads, like `index`; every
+ * other argument, the choice of the path, the checks and the refusals are those of rdst_sample_patches, and an all-zero
+ * `variant` gives its batch.  ONE launch, no atomics: the same bits on every run.  Slices are read with lanes along their
+ * rows and the outputs written with lanes along theirs; the transposed variants pass through 32 x 32 LDS blocks. */
+int rdst_sample_patches_d8(const float* stack, const uint8_t* labels, const int32_t* index, const int32_t* variant, float* hr,
+                           float* lr, uint8_t* label_out, int S, int C, int H, int W, int B, int hp, int lp,
+                           const int32_t* tap_index, const float* tap_weight, void* stream);
 
 /* ---- Tiled whole-slice inference (rdst_amd/tiling.py) ----------------------------------------------------------------------
  * The reference's ImageFolder / UnFolder / Folder (datasets/basic_dataset.py:347-449: nn.Unfold, the network on the patches,

@@ -99,6 +99,7 @@ SIGNATURES = {
     # bicubic degradation and the training-batch sampler (rdst_amd.data)
     "rdst_resize_bicubic": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "rdst_sample_patches": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "rdst_sample_patches_d8": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     # tiled whole-slice inference (rdst_amd.tiling)
     "rdst_unfold_tiles": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _l, _i, _p]),
     "rdst_fold_tiles": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),

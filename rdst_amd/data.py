@@ -10,6 +10,10 @@ slices are moved to the GPU once and a batch is cut and degraded where it is con
   * ``make_test_pair(hr, s)``        ``get_test_pair`` for one scale: what ``SRTester.evaluate`` / ``DPTrainStep.quick_eva`` take;
   * ``DevicePatchSampler``           ``__getitem__``: one HIP launch per batch (rdst_sample_patches), three random integers per
                                      patch drawn on the host, nothing read back; ``DPTrainStep.step_from(sampler)`` trains on it.
+                                     ``augment=True`` adds the random flips and transposes of the EDSR / RCAN / SwinIR recipes
+                                     (the eight of ``tiling.dihedral``, which the x8 self-ensemble averages over at test time),
+                                     one more integer per patch and still one launch (rdst_sample_patches_d8).  The reference
+                                     itself does not augment.
 
 The resize is what ``cv2.resize(INTER_CUBIC)`` computes on float images and what ``torch.nn.functional.interpolate(
 mode="bicubic", align_corners=False, antialias=False)`` computes: separable, four taps per axis, Keys kernel with a = -0.75,
@@ -18,7 +22,7 @@ overshoot below 0 and above 1 is kept, basic_dataset.py:74).  **cv2 is not insta
 resize to torch's float64 bicubic, and equality with cv2 is argued from its documented algorithm, not tested.
 
 Out of scope, and refused where they could be asked for: the Gaussian blur option (``blur_method='gaussian'``,
-cv2.GaussianBlur), augmentation, ``return_res_image``, reading volumes from disk.
+cv2.GaussianBlur), augmentation other than the eight flips / transposes, ``return_res_image``, reading volumes from disk.
 """
 from __future__ import annotations
 
@@ -167,10 +171,15 @@ def _as_stack(images, what: str, channels: bool) -> torch.Tensor:
 
 
 class Draw(NamedTuple):
-    """The random part of one batch: the scale, its HR patch size and the host copy of the index table."""
+    """The random part of one batch: the scale, its HR patch size, the host copy of the index table and, when the batch is
+    augmented, of the variant table."""
     sr_factor: float
     hr_patch_size: int
-    indices: torch.Tensor       # (B, 3) int32 on the host: slice, top, left
+    indices: torch.Tensor                       # (B, 3) int32 on the host: slice, top, left
+    variants: Optional[torch.Tensor] = None     # (B,) int32 on the host: the ``tiling.dihedral`` transform of every patch
+
+
+_AUGMENT = {False: 0, None: 0, True: 8, "d8": 8, "flip": 4}      # augment= -> how many of the eight transforms are drawn
 
 
 class DevicePatchSampler:
@@ -186,13 +195,28 @@ class DevicePatchSampler:
     ``[0, H - hp] x [0, W - hp]`` inclusive (:492-497).  Everything random comes from ``generator`` (a CPU torch.Generator), the
     3 B integers go to the device with a non-blocking copy from pinned memory, and one HIP launch writes the batch: the call
     neither waits for the device nor reads from it.  ``sample(out=(inputs, targets))`` writes into the caller's tensors.
+
+    ``augment``: ``False`` / ``None`` the sampler above; ``True`` / ``'d8'`` one of the eight transforms of ``tiling.dihedral``
+    per patch, uniformly (``k`` in 0..7: flip the columns if ``k & 1``, the rows if ``k & 2``, then transpose if ``k & 4``);
+    ``'flip'`` one of the four without the transpose.  Crop, then transform, then degrade: ``out[b] = dihedral(crop_b, k_b)``, the
+    label likewise, and ``in[b]`` is the resize of the TRANSFORMED patch, so ``in == bicubic_resize(out, lp)`` holds bit for bit
+    as it does without (resizing first and flipping afterwards would not give the same bits).  The ``B`` variants are drawn
+    after the integers above (without ``augment`` the generator is consumed exactly as before), travel with the origins in the
+    same pinned copy and are returned as ``batch['variants']`` (int32 ``(B,)`` on the host; the key exists only in an augmented
+    batch).  A ``draw=`` decides: ``Draw(..., variants=t)`` forces the transforms as it forces the origins, whatever
+    ``augment`` is, and a draw without variants gives a plain batch.
+
     ``device='cpu'`` keeps the slices on the host: ``draw()`` works, ``sample()`` raises (there is no CPU path)."""
 
     def __init__(self, hr_images, batch_size: int, lr_patch_size: int, sr_scales: Sequence[float] = (4.0,), labels=None,
-                 blur_method: Optional[str] = None, device="cuda", generator: Optional[torch.Generator] = None):
+                 blur_method: Optional[str] = None, device="cuda", generator: Optional[torch.Generator] = None,
+                 augment=False):
         if blur_method not in (None, ""):
             raise ValueError(f"DevicePatchSampler: blur_method={blur_method!r} is not supported (cv2.GaussianBlur is out of "
                              "scope; the shipped configuration has blur_method = '')")
+        if not isinstance(augment, (bool, str, type(None))) or augment not in _AUGMENT:
+            raise ValueError(f"DevicePatchSampler: augment={augment!r} is not one of False, True, 'd8', 'flip'")
+        self.n_variants = _AUGMENT[augment]
         self.batch_size, self.lr_patch_size = int(batch_size), int(lr_patch_size)
         self.sr_scales = [float(s) for s in sr_scales]
         if self.batch_size <= 0 or self.lr_patch_size <= 0 or not self.sr_scales:
@@ -236,11 +260,34 @@ class DevicePatchSampler:
         g, B = self.generator, self.batch_size
         k = int(torch.randint(len(self.sr_scales), (1,), generator=g)) if len(self.sr_scales) > 1 else 0
         hp = self.hr_patch_sizes[k]
-        tab = torch.empty(B, 3, dtype=torch.int32, pin_memory=self._pin)
+        if not self.n_variants:
+            tab = torch.empty(B, 3, dtype=torch.int32, pin_memory=self._pin)
+            var = None
+        else:       # one buffer, the variants behind the index table: sample() copies it to the device as it is
+            both = torch.empty(4 * B, dtype=torch.int32, pin_memory=self._pin)
+            tab, var = both[:3 * B].view(B, 3), both[3 * B:]
         tab[:, 0] = torch.randperm(self.S, generator=g)[:B]
         tab[:, 1] = torch.randint(0, self.H - hp + 1, (B,), generator=g)
         tab[:, 2] = torch.randint(0, self.W - hp + 1, (B,), generator=g)
-        return Draw(self.sr_scales[k], hp, tab)
+        if var is not None:
+            var[:] = torch.randint(0, self.n_variants, (B,), generator=g)
+        return Draw(self.sr_scales[k], hp, tab, var)
+
+    def _packed(self, d: Draw) -> torch.Tensor:
+        """The host buffer of an augmented draw, 4 B int32: the index table, then the variants.  A draw of ``draw()`` is one
+        already; forced tables are packed into a new one."""
+        B, idx, var = self.batch_size, d.indices, d.variants
+        both = getattr(var, "_base", None)      # draw()'s two views have the whole buffer as their base
+        if (both is not None and both is idx._base and both.dtype == torch.int32 and tuple(both.shape) == (4 * B,)
+                and tuple(idx.shape) == (B, 3) and idx.is_contiguous() and idx.data_ptr() == both.data_ptr()
+                and tuple(var.shape) == (B,) and var.data_ptr() == both.data_ptr() + 12 * B):
+            return both
+        if not isinstance(var, torch.Tensor) or var.is_cuda or var.is_floating_point() or tuple(var.shape) != (B,):
+            raise ValueError(f"DevicePatchSampler.sample: draw.variants must be a host tensor of {B} integers")
+        both = torch.empty(4 * B, dtype=torch.int32, pin_memory=self._pin)
+        both[:3 * B].view(B, 3).copy_(idx)
+        both[3 * B:].copy_(var)
+        return both
 
     def batch_shapes(self, draw: Draw):
         """(shape of 'in', shape of 'out') of the batch ``draw`` leads to."""
@@ -265,16 +312,26 @@ class DevicePatchSampler:
                             or not t.is_contiguous()):
                         raise ValueError(f"DevicePatchSampler.sample: out {name} must be a contiguous float32 {shape} tensor "
                                          f"on {self.device}")
-            index = d.indices.to(self.device, non_blocking=True)
+            if d.variants is None:
+                index, variant = d.indices.to(self.device, non_blocking=True), None
+            else:
+                index = self._packed(d).to(self.device, non_blocking=True)
+                variant = index.data_ptr() + 12 * self.batch_size        # the variants sit behind the 3 B int32 of the table
             lab = None
             if self.labels is not None:
                 lab = torch.empty(hr_shape[0], 1, hp, hp, dtype=torch.uint8, device=self.device)
             ti, tw = _device_table(hp, lp, self.device)
-            _lib.check(lib.rdst_sample_patches(
-                self.hr_images.data_ptr(), self.labels.data_ptr() if lab is not None else None, index.data_ptr(),
-                hr.data_ptr(), lr.data_ptr(), lab.data_ptr() if lab is not None else None, self.S, self.C, self.H, self.W,
-                self.batch_size, hp, lp, ti.data_ptr(), tw.data_ptr(), _stream()), "rdst_sample_patches")
+            tail = (hr.data_ptr(), lr.data_ptr(), lab.data_ptr() if lab is not None else None, self.S, self.C, self.H, self.W,
+                    self.batch_size, hp, lp, ti.data_ptr(), tw.data_ptr(), _stream())
+            stack, labels = self.hr_images.data_ptr(), self.labels.data_ptr() if lab is not None else None
+            if variant is None:
+                _lib.check(lib.rdst_sample_patches(stack, labels, index.data_ptr(), *tail), "rdst_sample_patches")
+            else:
+                _lib.check(lib.rdst_sample_patches_d8(stack, labels, index.data_ptr(), variant, *tail),
+                           "rdst_sample_patches_d8")
         batch = {"in": lr, "out": hr, "sr_factor": d.sr_factor, "real_sr_scale": hp / lp, "indices": d.indices}
+        if d.variants is not None:
+            batch["variants"] = d.variants
         if lab is not None:
             batch["label"] = lab.to(torch.int64)          # the dtype SegUNet_F('label-gt') takes
         return batch

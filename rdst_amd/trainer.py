@@ -284,7 +284,8 @@ class DPTrainStep:
         """``step()`` on a fresh batch of a ``rdst_amd.data.DevicePatchSampler`` (``last_batch`` keeps it).  Once a graph is
         captured and the batch has its shapes, the sampler writes straight into the tensors the graph reads, so ``step()``
         finds them in place and copies nothing; the sampler's launch is on the stream of the replay, so the previous replay
-        has finished reading them.  Labels stay in the batch for the caller's own loop: ``step()`` takes none."""
+        has finished reading them.  Labels stay in the batch for the caller's own loop: ``step()`` takes none.  An augmenting
+        sampler (``augment=True``) is taken as it is: its transformed batch lands in the same tensors."""
         draw = sampler.draw()
         out = None
         if (self.graph is not None and (self.device_guard or self.loss_threshold >= GUARD_OFF)

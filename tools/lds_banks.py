@@ -142,9 +142,28 @@ def d8_blocks():
     return rows
 
 
+def sampler_d8():
+    """rdst_amd/csrc/sampler.hip: sample4_d8_kernel / sample_tab_d8_kernel.  Their 32 x 32 blocks are the ones of d8_blocks()
+    (thread = (r = tid / 8, q = tid % 8) in the 16-byte flavours, (tid / 32, tid % 32) in the scalar one; a flip mirrors r or
+    the column inside the block, which permutes the banks of a lane group); sample4_d8_kernel adds hs[32][10], the horizontal
+    sums: written at [r][q], read by lane = (oy = l / 8, ox = l % 8) at [4 oy + j][ox]."""
+    rows = []
+    for e in (0, 3):
+        rows.append((f"mirrored column read [31-(4q+{e})][31-r]", "read_b32",
+                     lambda l, e=e: 4 * ((31 - 4 * (l & 7) - e) * 33 + 31 - (l >> 3)), "the flipped transposed variants"))
+    rows += [
+        ("hs write [r][q]", "write_b32", lambda l: 4 * ((l >> 3) * 10 + (l & 7)), "1 per thread (2-way on a write is free)"),
+        ("hs read [4oy+1][ox]", "read_b32", lambda l: 4 * ((4 * (l >> 3) + 1) * 10 + (l & 7)), "4 in the first wave"),
+        ("(hs rows of 9: the same read)", "read_b32", lambda l: 4 * ((4 * (l >> 3) + 1) * 9 + (l & 7)), "what the second pad avoids"),
+    ]
+    return rows
+
+
 if __name__ == "__main__":
     print("== tiles.hip d8 blocks (rows of 33 floats)")
     report(d8_blocks())
+    print("== sampler.hip d8 kernels (the same blocks; hs rows of 10 floats)")
+    report(sampler_d8())
     for nct in (2, 3, 4):
         print(f"== mlp_bwd_kernel<{nct}> (C = {30 * nct})")
         report(mlp_bwd(nct))
