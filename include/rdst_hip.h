@@ -201,7 +201,7 @@ int rdst_mlp_bwd(const void* X, int64_t ld_x, const float* ln_w, const float* ln
  *   Wc : fp32 (Cout, Cin, k, k) as nn.Conv2d stores it.   R/Y rows are in the OUTPUT geometry.
  */
 /*   workspace : rdst_conv_fwd_workspace(Cin, Cout, ksize) bytes of device scratch (16-byte aligned) for the bf16
- *               fragment-major image of the weights that the register-stationary 3x3 kernels read (conv3_mfma.hip);
+ *               fragment-major image of the weights that the register-stationary 3x3 kernels read (conv3_kernel.h);
  *               NULL / 0 selects the kernels that stage the fp32 weights themselves. */
 size_t rdst_conv_fwd_workspace(int Cin, int Cout, int ksize);
 int rdst_conv_fwd(const void* X, int64_t ld_x, int in_act, const float* Wc, const float* bias,

@@ -63,7 +63,7 @@ int conv_in1_wgrad_bf16(const bf16* X, int64_t ldx, int in_act, const bf16* dY, 
                         const ConvGeom& g, float s, hipStream_t st);
 size_t conv_in1_slab_floats(int Cout);
 
-// register-stationary 3x3 kernels for the E1 shapes, bf16 (conv3_mfma.hip); RDST_ENOTSUP for everything else.
+// register-stationary 3x3 kernels for the E1 shapes, bf16 (conv3_kernel.h, entry points in conv3_mfma.hip); RDST_ENOTSUP for everything else.
 // wpack: conv3_pack_bytes(Cin, Cout) bytes of 16-byte aligned device scratch (NULL -> RDST_ENOTSUP).
 size_t conv3_pack_bytes(int Cin, int Cout);
 int conv3_fwd_shape(int Cin, int Cout, int ks, int r, bool has_res, int in_act);   // 0 = not covered
@@ -75,7 +75,7 @@ size_t conv3_wgrad_slab_bytes(int Cin, int Cout);
 int conv3_wgrad_bf16(const bf16* X, int64_t ldx, int in_act, const bf16* dY, int64_t lddy, float* dW, float* dbias, float* slab,
                      const ConvGeom& g, float s, hipStream_t st);
 
-// the same register-stationary kernels on fp32 rows in the RDST_F32X3 arithmetic (conv3x_mfma.hip); wpack: conv3x_pack_bytes bytes
+// the same kernel source on fp32 rows in the RDST_F32X3 arithmetic (entry points in conv3x_mfma.hip); wpack: conv3x_pack_bytes bytes
 size_t conv3x_pack_bytes(int Cin, int Cout);
 int conv3x_fwd_shape(int Cin, int Cout, int ks, int r, bool has_res, int in_act);   // 0 = not covered
 int conv3x_fwd_f32(const float* X, int64_t ldx, int in_act, const float* Wc, const float* bias, const float* R, int64_t ldr,

@@ -5,7 +5,7 @@
 // for the 150 -> 60 fusion conv — less than a CU's 512 KB register file.  So a workgroup (8 waves, 2 per SIMD) owns a set
 // of pixels and ALL 9 taps; wave w keeps its 9-12 output tiles (32 output channels x 32 input channels of one tap) as
 // MFMA accumulators from the first pixel to the last and nothing but the two operand streams moves:
-//   * pixels are cut into the strips of conv3_mfma.hip (32 wide, SH rows high); X rows (34 pixels with the halo) and dY
+//   * pixels are cut into the strips of conv3_kernel.h (32 wide, SH rows high); X rows (34 pixels with the halo) and dY
 //     rows roll through two LDS rings, filled by LDS-DMA (buffer_load ... lds, out-of-range lanes write zeros: image
 //     border, pad slots, tensor end), RPS rows per step, one barrier per step, the next step's rows in flight;
 //   * both operands have the contraction index (pixel) as their ROW in memory: fragments are read transposed with
@@ -19,7 +19,7 @@
 // slabs in fixed order (deterministic), applies s, and scatters into nn.Conv2d's (Cout, Cin, 3, 3) layout.
 // The old stripe kernel (conv_mfma.hip) split the taps over three workgroups per pixel range, read X and dY three
 // times and staged them through registers: 138 us average per launch for the same work.
-#include "conv.h"
+#include "conv3_host.h"
 #include "lds_dma.h"
 #include "mfma.h"
 
@@ -245,16 +245,9 @@ __global__ void __launch_bounds__(256) conv3_wgrad_reduce_kernel(const float* __
 template <int CI, int CO, bool UNSHUF>
 int launch_w3(W3Args& p, float s, float* dW, float* dbias, hipStream_t st, const char* what) {
   using CF = W3Cfg<CI, CO, UNSHUF>;
-  int SH = 16;
-  auto count = [&](int sh) { return (int64_t)p.B * ((p.H + sh - 1) / sh) * (p.W / 32); };
-  const int want = 256 / CF::ROLES;
-  while (count(SH) < want && SH > CF::RPS) SH /= 2;
-  p.SH = SH;
-  p.nys = (p.H + SH - 1) / SH;
-  const int64_t ns = count(SH);
-  if (ns >= (1ll << 31)) return RDST_ENOTSUP;
-  p.nstrips = (int)ns;
-  p.npg = ns < want ? (int)ns : want;
+  Conv3Strips sp;
+  if (!conv3_strip_plan(p.B, p.H, p.W, CF::RPS, 256 / CF::ROLES, sp)) return RDST_ENOTSUP;
+  p.SH = sp.SH; p.nys = sp.nys; p.nstrips = sp.nstrips; p.npg = sp.npg;
   const int grid = p.npg * CF::ROLES;
   auto kern = conv3_wgrad_kernel<CI, CO, UNSHUF>;
   if (int rc = rdst_launch(kern, dim3((unsigned)grid), dim3(512), CF::SMEM, st, what, p)) return rc;
@@ -262,8 +255,6 @@ int launch_w3(W3Args& p, float s, float* dW, float* dbias, hipStream_t st, const
   return rdst_launch(conv3_wgrad_reduce_kernel<CI, CO, UNSHUF>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, "conv3_wgrad_reduce",
                      p.slab, p.npg, s, dW, dbias);
 }
-
-bool rows_ok(const void* ptr, int64_t ld) { return ((uintptr_t)ptr & 3) == 0 && (ld & 1) == 0; }
 
 }  // namespace
 
@@ -279,13 +270,9 @@ size_t conv3_wgrad_slab_bytes(int Cin, int Cout) {
 // RDST_ENOTSUP = not one of the covered shapes.  dY in the output geometry (pixel-shuffled when g.r == 2).
 int conv3_wgrad_bf16(const bf16* X, int64_t ldx, int in_act, const bf16* dY, int64_t lddy, float* dW, float* dbias, float* slab,
                      const ConvGeom& g, float s, hipStream_t st) {
-  if (!slab || g.ks != 3 || g.pad != 1 || in_act || g.W % 32 || ((uintptr_t)slab & 15)) return RDST_ENOTSUP;
-  if (!rows_ok(X, ldx) || !rows_ok(dY, lddy)) return RDST_ENOTSUP;
-  int shape = 0;
-  if (g.Cin == 150 && g.Cout == 60 && g.r == 1) shape = 1;
-  else if (g.Cin == 60 && g.Cout == 60 && g.r == 1) shape = 2;
-  else if (g.Cin == 60 && g.Cout == 240 && g.r == 2 && lddy == 60) shape = 3;
-  if (!shape) return RDST_ENOTSUP;
+  if (!conv3_bwd_geom_ok(g, in_act, slab) || !conv3_rows_ok(X, ldx) || !conv3_rows_ok(dY, lddy)) return RDST_ENOTSUP;
+  const int shape = conv3_bwd_shape(g.Cin, g.Cout, g.r);
+  if (!shape || (shape == 3 && lddy != 60)) return RDST_ENOTSUP;   // (sub-pixel pairs contiguous in dY)
   const int64_t xb = ((g.pixels() - 1) * ldx + g.Cin) * 2;
   const int64_t yb = ((g.pixels() * g.r * g.r - 1) * lddy + g.Cout / (g.r * g.r)) * 2;
   if (xb >= (1ll << 31) || yb >= (1ll << 31)) return RDST_ENOTSUP;

@@ -14,7 +14,7 @@
 //   * the gradient of conv + PixelShuffle(2) (60 -> 240) runs as FOUR launches of the 60 -> 60 form, one per sub-pixel q = 2 i + j: dY
 //     seen through a stride-2 pixel view of the shuffled tensor, output channels 4 c' + q;
 //   * fp32 slabs, summed in fixed order by conv3x_wgrad_reduce (deterministic), scale applied, scattered into (Cout, Cin, 3, 3).
-#include "conv.h"
+#include "conv3_host.h"
 #include "lds_dma.h"
 #include "mfma.h"
 
@@ -252,15 +252,9 @@ __global__ void __launch_bounds__(256) conv3x_wgrad_reduce_kernel(const float* _
 template <int CI, int CO>
 int launch_w3x(W3XArgs& p, float s, int cmul, int coff, float* dW, float* dbias, hipStream_t st, const char* what) {
   using CF = W3X<CI, CO>;
-  int SH = 16;
-  auto count = [&](int sh) { return (int64_t)p.B * ((p.H + sh - 1) / sh) * (p.W / 32); };
-  while (count(SH) < 256 && SH > 2) SH /= 2;
-  p.SH = SH;
-  p.nys = (p.H + SH - 1) / SH;
-  const int64_t ns = count(SH);
-  if (ns >= (1ll << 31)) return RDST_ENOTSUP;
-  p.nstrips = (int)ns;
-  p.npg = ns < 256 ? (int)ns : 256;
+  Conv3Strips sp;
+  if (!conv3_strip_plan(p.B, p.H, p.W, 2, 256, sp)) return RDST_ENOTSUP;
+  p.SH = sp.SH; p.nys = sp.nys; p.nstrips = sp.nstrips; p.npg = sp.npg;
   auto kern = conv3x_wgrad_kernel<CI, CO>;
   if (int rc = rdst_launch(kern, dim3((unsigned)p.npg), dim3(512), CF::SMEM, st, what, p)) return rc;
   return rdst_launch(conv3x_wgrad_reduce_kernel<CI, CO>, dim3((unsigned)((CF::SLABF + 255) / 256)), dim3(256), 0, st, "conv3x_wgrad_reduce",
@@ -272,12 +266,8 @@ int launch_w3x(W3XArgs& p, float s, int cmul, int coff, float* dW, float* dbias,
 // RDST_ENOTSUP = not one of the covered shapes.  dY in the output geometry (pixel-shuffled when g.r == 2).  slab: conv3_wgrad_slab_bytes.
 int conv3x_wgrad_f32(const float* X, int64_t ldx, int in_act, const float* dY, int64_t lddy, float* dW, float* dbias, float* slab,
                      const ConvGeom& g, float s, hipStream_t st) {
-  if (!slab || g.ks != 3 || g.pad != 1 || in_act || g.W % 32 || ((uintptr_t)slab & 15)) return RDST_ENOTSUP;
-  if (((uintptr_t)X & 3) || ((uintptr_t)dY & 3)) return RDST_ENOTSUP;
-  int shape = 0;
-  if (g.Cin == 150 && g.Cout == 60 && g.r == 1) shape = 1;
-  else if (g.Cin == 60 && g.Cout == 60 && g.r == 1) shape = 2;
-  else if (g.Cin == 60 && g.Cout == 240 && g.r == 2) shape = 3;
+  if (!conv3_bwd_geom_ok(g, in_act, slab) || !conv3_rows_ok(X, ldx) || !conv3_rows_ok(dY, lddy)) return RDST_ENOTSUP;
+  const int shape = conv3_bwd_shape(g.Cin, g.Cout, g.r);
   if (!shape) return RDST_ENOTSUP;
   const int64_t xb = ((g.pixels() - 1) * ldx + g.Cin) * 4;
   const int64_t yb = ((g.pixels() * g.r * g.r - 1) * lddy + g.Cout / (g.r * g.r)) * 4;

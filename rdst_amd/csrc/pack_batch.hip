@@ -28,7 +28,7 @@ __global__ void __launch_bounds__(256) pack_batch_kernel(const PackBatch bt) {
   } else if (J.kind == RDST_PACK_CONV3_FWD_X3) {
     conv3x_pack_block(bid, J.W, reinterpret_cast<uint32_t*>(J.out), J.K, J.N, J.K, J.N, (J.K + 15) / 16, (J.N + 31) / 32, PK_FWD, J.s);
   } else if (J.kind == RDST_PACK_LINEAR_SEC3) {
-    const int nt = lin3sec_tiles(J.K, J.N, 3), ks = (J.K + 15) / 16;
+    const int nt = lin3sec_tiles(J.N, 3), ks = (J.K + 15) / 16;
     bf16* wp = reinterpret_cast<bf16*>(J.out);
     float* sb = reinterpret_cast<float*>(reinterpret_cast<char*>(J.out) + (size_t)nt * ks * 1024);
     lin3sec_pack_block(bid, J.W, J.gamma, J.beta, J.bias, wp, sb, J.N, J.K, 3, J.s);

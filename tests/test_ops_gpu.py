@@ -104,6 +104,11 @@ CONV = [  # B, H, W, Cin, Cout, k, act, residual, scale, shuffle
     (1, 8, 32, 150, 60, 3, 0, True, 0.7, 1),   # fusion conv on full 32-pixel row slabs (fp32: two launches over halves of the input channels)
     (1, 4, 32, 60, 240, 3, 0, False, 1.0, 2),  # upsampler conv, 32-pixel row slabs (fp32 data gradient: two launches over halves of dY's channels)
     (1, 6, 10, 150, 60, 3, 2, True, 1.0, 1),   # the same split on the pixel-tile kernel, reading through LeakyReLU
+    # 33 x ceil(6 / 16) x 8 = 264 strips on a grid capped at 256: eight workgroups of the register-stationary kernels run a second
+    # strip that belongs to another image (the row ring is primed again); 6 rows = one ragged strip (3 steps of 2 rows, 1 1/2 of 4)
+    (33, 6, 256, 150, 60, 3, 0, True, 0.7, 1),
+    (33, 6, 256, 60, 60, 3, 0, True, 0.5, 1),
+    (33, 6, 256, 60, 240, 3, 0, False, 1.0, 2),
 ]
 
 

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""usage: tools/isa_diff.py OLD_CSRC NEW_CSRC [--debug] [-D NAME ...] [--only REGEX]
+"""usage: tools/isa_diff.py OLD_CSRC NEW_CSRC [--debug] [-D NAME ...] [--only REGEX] [--rename REGEX=REPL ...]
 Is the device code of two csrc trees the same?  Every .hip of both directories is compiled with the build's flags plus
 -S --cuda-device-only; lines naming __hip_cuid_ (a hash of the translation unit) are dropped.  --debug adds -DRDST_DEBUG,
 -D further switches (LB3_STAMPS, ...), --only keeps the file names that match.  Per file: `identical`, or the kernels whose
 text differs, each with the kernel-resource-usage numbers of both sides (dynamic LDS is not in `LDS Size`).  Exit status 1 if
 anything differs or fails to compile.
+--rename REGEX=REPL (repeatable) rewrites the OLD side's text before the comparison: a kernel whose symbol changed (a new template
+argument, another argument type) is paired with its successor.  Mangled names carry length prefixes: match the mangled text.
 OLD_CSRC is a directory: take the parent's from `git worktree add` or `git archive` (it needs ../../include next to it)."""
 import argparse, os, re, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
@@ -32,12 +34,19 @@ def compile_one(src, out, extra):
     return res, ""
 
 
-def sections(path):
+def renamed(text, renames):
+    for rx, repl in renames:
+        text = rx.sub(repl, text)
+    return text
+
+
+def sections(path, renames=()):
     """{function symbol: its lines (body and kernel descriptor)}; everything outside a function under ''"""
     sec, cur = {"": []}, ""
     for l in open(path):
         if "__hip_cuid_" in l:
             continue
+        l = renamed(l, renames)
         m = re.match(r"\s*\.type\s+(\S+),@function", l) or re.match(r"\s*\.amdhsa_kernel\s+(\S+)", l)
         if m:
             cur = m.group(1)
@@ -62,7 +71,9 @@ def main():
     ap.add_argument("--debug", action="store_true")
     ap.add_argument("-D", dest="defs", action="append", default=[])
     ap.add_argument("--only", default=".")
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPL")
     a = ap.parse_args()
+    renames = [(re.compile(rx), repl) for rx, _, repl in (r.partition("=") for r in a.rename)]
     extra = (["-DRDST_DEBUG"] if a.debug else []) + ["-D" + d for d in a.defs]
     files = sorted({f for d in (a.old, a.new) for f in os.listdir(d) if f.endswith(".hip") and re.search(a.only, f)})
     bad = 0
@@ -84,7 +95,8 @@ def main():
                 print(f"{f}: does not compile ({'old' if ro is None else 'new'})\n{eo or en}")
                 bad += 1
                 continue
-            so, sn = sections(os.path.join(tmp, f"old_{f}.s")), sections(os.path.join(tmp, f"new_{f}.s"))
+            ro = {renamed(k, renames): v for k, v in ro.items()}
+            so, sn = sections(os.path.join(tmp, f"old_{f}.s"), renames), sections(os.path.join(tmp, f"new_{f}.s"))
             diff = [k for k in sorted(set(so) | set(sn)) if so.get(k) != sn.get(k)]
             if not diff:
                 print(f"{f}: identical")

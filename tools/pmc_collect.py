@@ -34,7 +34,7 @@ KERNELS = {
     "wattn_fwd_hd_kernel": ("wattn_fwd_hd_kernel", ["wattn_mfma_hd.hip", "wattn_hd.h"]),
     "wattn_bwd_hd_kernel": ("wattn_bwd_hd_kernel", ["wattn_bwd_mfma_hd.hip", "wattn_hd.h"]),
     "wattn_bwd_pair_kernel": ("wattn_bwd_pair_kernel", ["wattn_bwd_pair.hip", "wattn_hd.h"]),
-    "conv3_kernel": ("conv3_kernel", ["conv3_mfma.hip"]),
+    "C3Bf16": ("conv3_kernel", ["conv3_kernel.h", "conv3_mfma.hip"]),       # conv3_kernel<C3Bf16, ...>: see main()
     "conv3_wgrad_kernel": ("conv3_wgrad_kernel", ["conv3_wgrad.hip"]),
     "lin_mfma_kernel": ("lin_mfma_kernel", ["linear_mfma.hip"]),
     "mlp_fwd_kernel": ("mlp_fwd_kernel", ["mlp_mfma.hip"]),
@@ -49,7 +49,7 @@ KERNELS = {
     "wattn16_bwd1_kernel": ("wattn16_bwd1_kernel", ["wattn16_mfma.hip", "wattn_hd.h"]),
     "lin3x_kernel": ("lin3x_kernel", ["lin3x_mfma.hip"]),
     "lnlin3x_bwd_kernel": ("lnlin3x_bwd_kernel", ["lnlin3x_mfma.hip"]),
-    "conv3x_kernel": ("conv3x_kernel", ["conv3x_mfma.hip"]),
+    "C3X3": ("conv3x_kernel", ["conv3_kernel.h", "conv3x_mfma.hip"]),        # conv3_kernel<C3X3, ...>
     "conv3x_wgrad_kernel": ("conv3x_wgrad_kernel", ["conv3x_wgrad.hip"]),
     "wattn_fwd_mfma_kernel": ("wattn_fwd_mfma_kernel", ["wattn_mfma.hip"]),
     "wattn_bwd_mfma_kernel": ("wattn_bwd_mfma_kernel", ["wattn_bwd_mfma.hip"]),
@@ -94,7 +94,8 @@ def main():
             for row in csv.DictReader(fh):
                 name = row["Kernel_Name"]
                 for sub, (key, _) in KERNELS.items():
-                    if sub in name and (sub not in ("conv3_kernel", "conv3x_kernel") or "wgrad" not in name):
+                    # the two arithmetics of conv3_kernel.h are told apart by their policy type, however the namespace is printed
+                    if sub in name and (sub not in ("C3Bf16", "C3X3") or "conv3_kernel<" in name):
                         short = re.sub(r"\(anonymous namespace\)::|void ", "", name).split("(")[0]
                         agg.setdefault(key, {}).setdefault(short, {}).setdefault(row["Counter_Name"], []).append(float(row["Counter_Value"]))
     out = {"command": "rocprofv3 --kernel-trace --pmc <one set per run> -- python3 bench.py --steps 1 --warmup 0 --graph 0 "
