@@ -597,6 +597,38 @@ int rdst_adam_step_dev(float* param, const float* grad, float* exp_avg, float* e
                        rdst_lr_schedule sched, float beta1, float beta2, float eps, float weight_decay,
                        rdst_step_state* state, void* stream);
 
+/* ---- weight EMA: updated inside fused Adam, exchanged in place for evaluation ---------------------------------------------
+ * The third part of the EDSR / RCAN / SwinIR recipe next to augmentation and the self-ensemble (BasicSR and SwinIR use
+ * ema_decay = 0.999); the reference keeps no EMA, so this is an addition to its loop, off by default.  No PSNR gain is
+ * claimed here: there are no trained weights or real volumes to measure one on.
+ *
+ * `ema` is one more flat fp32 buffer of n elements beside param.  The two entry points below are rdst_adam_step and
+ * rdst_adam_step_dev with, per element, AFTER p has its new value,
+ *     e = fmaf(p_new - e, omd, e),      omd = (float)(1.0 - d_t),
+ *     d_t = ema_decay                                    (ema_warmup == 0)
+ *     d_t = min(ema_decay, (1 + t) / (10 + t))           (ema_warmup != 0),
+ * d_t and 1 - d_t in double, rounded to fp32 once.  t = step (rdst_adam_step_ema, on the host) or state->kept
+ * (rdst_adam_step_dev_ema, by thread 0 of each block next to the bias corrections).  The parameter and moment
+ * expressions are those of the siblings, operation for operation: param, exp_avg and exp_avg_sq receive the bits the
+ * sibling writes for the same inputs.  A skipped step (state->last_keep == 0) returns before touching anything, ema
+ * included, so t counts applied updates only.  The arguments of rdst_adam_step_dev_ema never change between steps: a
+ * captured launch replays as it is.  20 B read + 16 B written per element (8 B more than the siblings), 16-byte accesses, the siblings' grid-stride
+ * loop and scalar tail of n % 4 elements, no atomics.
+ * Checks, all before any launch: the siblings' own, plus ema non-null and 16-byte aligned and ema_decay in [0, 1)
+ * (RDST_EINVAL otherwise; a NaN decay is refused). */
+int rdst_adam_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                       float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
+                       double ema_decay, int ema_warmup, void* stream);
+int rdst_adam_step_dev_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                           rdst_lr_schedule sched, float beta1, float beta2, float eps, float weight_decay,
+                           double ema_decay, int ema_warmup, rdst_step_state* state, void* stream);
+
+/* Exchanges two fp32 buffers of n elements in place (16-byte accesses plus a scalar tail): evaluation on the averaged
+ * weights is swap(param, ema), the forwards, swap again.  No address changes, so packed-weight plans and captured graphs
+ * that name param stay valid and pick the other values up through their own pack-refresh node.  RDST_EINVAL for a null
+ * or misaligned (16 B) pointer, n < 0, or ranges that overlap. */
+int rdst_swap_f32(float* a, float* b, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -109,6 +109,10 @@ SIGNATURES = {
     "rdst_step_guard_workspace": (_z, [_l]),
     "rdst_step_guard": (_i, [_p, C.c_double, _p, _p, _l, C.c_double, _i, _p, _z, _p, _p]),
     "rdst_adam_step_dev": (_i, [_p, _p, _p, _p, _l, LrSchedule, _f, _f, _f, _f, _p, _p]),
+    # the weight EMA (rdst_amd.optim.FlatAdam(ema_decay=...)): additive entry points, the ABI version stays
+    "rdst_adam_step_ema": (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _l, C.c_double, _i, _p]),
+    "rdst_adam_step_dev_ema": (_i, [_p, _p, _p, _p, _p, _l, LrSchedule, _f, _f, _f, _f, C.c_double, _i, _p, _p]),
+    "rdst_swap_f32": (_i, [_p, _p, _l, _p]),
 }
 
 ABI_VERSION = 11             # must equal rdst_abi_version() of the loaded library (argument lists change between versions)

@@ -11,6 +11,7 @@
 
 namespace {
 
+// (ema.hip restates this kernel with the EMA stream added: mirror an edit there)
 __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, int64_t n, float lr_bc1,
                                                    float beta1, float beta2, float eps, float wd, float sqrt_bc2) {

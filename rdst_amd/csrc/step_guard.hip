@@ -84,6 +84,7 @@ __global__ void __launch_bounds__(kThreads) decide_kernel(const float* __restric
   st->last_sumsq = sumsq;
 }
 
+// (ema.hip restates adam_one and adam_dev_kernel's loop with the EMA stream added: mirror an edit there)
 __device__ __forceinline__ float adam_one(float& p, float g, float& m, float& v, float clip, float wd, float omb1,
                                           float omb2, float beta2, float eps, float lr_bc1, float sqrt_bc2) {
   const float gc = g * clip;      // clip == 1 leaves the bits of g as they are

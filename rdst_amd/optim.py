@@ -13,10 +13,17 @@ so the optimizer part of a reference ``checkpoint.tar`` (models/basic_trainer.py
 reference's update guard (models/trans_sr_trainer.py:162-174) in device memory (``rdst_step_guard`` +
 ``rdst_adam_step_dev``, include/rdst_hip.h): ``guard()`` and ``step()`` enqueue launches whose arguments never change,
 so both are graph-capturable, and nothing is read back until ``sync_host()``.
+
+``FlatAdam(ema_decay=d)`` keeps an exponential moving average of the parameters (BasicSR / SwinIR: 0.999) in one more flat
+fp32 buffer, updated INSIDE the same launch (``rdst_adam_step_ema`` / ``rdst_adam_step_dev_ema``) while the new parameter
+is in registers: ``e += (p_new - e) * (1 - d_t)``.  ``swap_ema()`` / ``ema_scope()`` exchange the two buffers in place
+(``rdst_swap_f32``) for evaluation: no address moves, so pack plans and captured graphs stay valid.  The reference keeps no
+EMA; it is off by default and no PSNR gain is claimed for it here.
 """
 from __future__ import annotations
 
 import bisect
+import contextlib
 import math
 from typing import Iterable, Optional, Sequence
 
@@ -49,10 +56,22 @@ def scheduler_fields(kept: int, table: Sequence[float], milestones: Sequence[int
             "_last_lr": [table[bisect.bisect_right(list(milestones), int(kept))]]}
 
 
+def ema_decay_at(t: int, decay: float, warmup: bool = False) -> float:
+    """The EMA decay of update ``t`` (1-based count of APPLIED updates) in double, as the kernels derive it
+    (include/rdst_hip.h): ``decay``, or with ``warmup`` ``min(decay, (1 + t) / (10 + t))``."""
+    d = float(decay)
+    if warmup:
+        d = min(d, (1.0 + float(t)) / (10.0 + float(t)))
+    return d
+
+
 class FlatAdam(torch.optim.Optimizer):
     def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 1e-4, betas=(0.9, 0.99), eps: float = 1e-8,
-                 weight_decay: float = 0.0, bucket: Optional[FlatGradBucket] = None, device_state: bool = False):
+                 weight_decay: float = 0.0, bucket: Optional[FlatGradBucket] = None, device_state: bool = False,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False):
         params = [p for p in params if p.requires_grad]
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"FlatAdam: ema_decay {ema_decay} is not in [0, 1)")
         if bucket is not None and [id(p) for p in bucket.params] != [id(p) for p in params]:
             raise ValueError("FlatAdam: the gradient bucket must hold exactly these parameters, in this order")
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
@@ -85,6 +104,11 @@ class FlatAdam(torch.optim.Optimizer):
                 self.flat_param[off:off + k].copy_(p.data.reshape(-1))
                 p.data = self.flat_param[off:off + k].view_as(p)  # the module now computes from the flat buffer
                 off += k
+        # the weight EMA: one more flat buffer, a copy of the parameters as they are now; nothing without ema_decay
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.ema_active = False                    # True while flat_param holds the averaged weights (swap_ema)
+        self.ema = self.flat_param.clone() if self.ema_decay is not None else None
         self._point_state()
 
     def _point_state(self) -> None:
@@ -107,32 +131,83 @@ class FlatAdam(torch.optim.Optimizer):
                 loss = closure()
         if not self.flat_param.is_cuda:
             raise RuntimeError("rdst_amd.optim.FlatAdam.step: the fused update is a HIP kernel; there is no CPU fallback")
+        if self.ema_active:
+            raise RuntimeError("FlatAdam.step: the parameters hold the averaged weights (swap_ema / ema_scope is active); "
+                               "the network must not train on them")
         if not self.bucket.check_views():
             raise RuntimeError("FlatAdam.step: p.grad no longer aliases the gradient bucket "
                                "(use bucket.zero() / bucket.detach_grads()+gather(), not zero_grad(set_to_none=True))")
         g = self.param_groups[0]
         lib = _lib.load()
+        ema = self.ema is not None      # the *_ema entry points: the buffer right behind the moments, decay and warmup last
+        bufs = [self.flat_param.data_ptr(), self.bucket.flat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr()]
+        if ema:
+            bufs.append(self.ema.data_ptr())
+        hyper = [float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"])]
+        ema_args = [self.ema_decay, int(self.ema_warmup)] if ema else []
+        n, stream = self.flat_param.numel(), torch.cuda.current_stream().cuda_stream
         if self.device_state:
             if not self._guard_pending:     # no guard() before this step: it is kept
                 self.guard(None, 0.0)
             self._guard_pending = False
-            _lib.check(lib.rdst_adam_step_dev(self.flat_param.data_ptr(), self.bucket.flat.data_ptr(),
-                                              self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.flat_param.numel(),
-                                              self._c_schedule(), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
-                                              float(g["weight_decay"]), self._dev_state.data_ptr(),
-                                              torch.cuda.current_stream().cuda_stream), "rdst_adam_step_dev")
+            name = "rdst_adam_step_dev_ema" if ema else "rdst_adam_step_dev"
+            _lib.check(getattr(lib, name)(*bufs, n, self._c_schedule(), *hyper, *ema_args, self._dev_state.data_ptr(), stream),
+                       name)
             return loss
         self._steps += 1
-        _lib.check(lib.rdst_adam_step(self.flat_param.data_ptr(), self.bucket.flat.data_ptr(), self.exp_avg.data_ptr(),
-                                      self.exp_avg_sq.data_ptr(), self.flat_param.numel(), float(g["lr"]),
-                                      float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
-                                      float(g["weight_decay"]), self._steps,
-                                      torch.cuda.current_stream().cuda_stream), "rdst_adam_step")
+        name = "rdst_adam_step_ema" if ema else "rdst_adam_step"
+        _lib.check(getattr(lib, name)(*bufs, n, float(g["lr"]), *hyper, self._steps, *ema_args, stream), name)
         self._step_t.fill_(float(self._steps))
         return loss
 
     def zero_grad(self, set_to_none: bool = False) -> None:  # noqa: D401 - keeps p.grad aliased to the bucket
         self.bucket.zero()
+
+    # ---- the weight EMA (ema_decay=...) ------------------------------------------------------------------------------
+    def _need_ema(self, what: str) -> None:
+        if self.ema is None:
+            raise RuntimeError(f"FlatAdam.{what}: needs FlatAdam(ema_decay=...)")
+
+    @torch.no_grad()
+    def reset_ema(self) -> None:
+        """``ema <- flat_param`` (the state a fresh optimizer has); refused while the two are exchanged."""
+        self._need_ema("reset_ema")
+        if self.ema_active:
+            raise RuntimeError("FlatAdam.reset_ema: swap_ema / ema_scope is active")
+        self.ema.copy_(self.flat_param)
+
+    @torch.no_grad()
+    def swap_ema(self) -> None:
+        """Exchange ``flat_param`` and ``ema`` in place (ONE ``rdst_swap_f32``) and toggle ``ema_active``.  Every parameter
+        of the network is a view of ``flat_param``, so the network computes from the averaged weights until the next call;
+        no address moves, so pack plans and captured graphs (whose pack refresh is one of their nodes) stay valid."""
+        self._need_ema("swap_ema")
+        if not self.flat_param.is_cuda:
+            raise RuntimeError("rdst_amd.optim.FlatAdam.swap_ema: the exchange is a HIP kernel; there is no CPU fallback")
+        _lib.check(_lib.load().rdst_swap_f32(self.flat_param.data_ptr(), self.ema.data_ptr(), self.flat_param.numel(),
+                                             torch.cuda.current_stream().cuda_stream), "rdst_swap_f32")
+        self.ema_active = not self.ema_active
+
+    @contextlib.contextmanager
+    def ema_scope(self):
+        """``with opt.ema_scope():`` the network holds the averaged weights inside; swapped back on exit, also when the body
+        raises.  ``step()`` and ``guard()`` raise inside."""
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
+
+    def ema_views(self) -> list:
+        """Per-parameter views of ``ema``, in parameter order.  Inside ``ema_scope()`` the buffers are exchanged: these
+        views then show the live weights and the parameters the averaged ones."""
+        self._need_ema("ema_views")
+        out, off = [], 0
+        for p in self.param_groups[0]["params"]:
+            k = p.numel()
+            out.append(self.ema[off:off + k].view_as(p))
+            off += k
+        return out
 
     # ---- device-resident step state (device_state=True) ------------------------------------------------------------
     def _need_device_state(self, what: str) -> None:
@@ -180,6 +255,8 @@ class FlatAdam(torch.optim.Optimizer):
         ``skip_nonfinite``, the gradient bucket is finite; ``max_grad_norm`` sets the clip coefficient the step applies.
         Call it once the bucket holds the (averaged) gradient."""
         self._need_device_state("guard")
+        if self.ema_active:
+            raise RuntimeError("FlatAdam.guard: the parameters hold the averaged weights (swap_ema / ema_scope is active)")
         if not self.flat_param.is_cuda:
             raise RuntimeError("rdst_amd.optim.FlatAdam.guard: the guard is a HIP kernel; there is no CPU fallback")
         if loss is not None and (loss.dtype != torch.float32 or loss.device != self.flat_param.device or loss.numel() != 1):
@@ -225,6 +302,8 @@ class FlatAdam(torch.optim.Optimizer):
         self._guard_pending = False
 
     def state_dict(self):
+        """torch.optim.Adam's layout.  The EMA is NOT in it, so reference checkpoints cross-load (the trainer saves it
+        under a key of its own)."""
         if self.device_state:
             self.sync_host()
         return super().state_dict()

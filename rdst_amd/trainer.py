@@ -21,6 +21,7 @@ reference ``checkpoint.tar`` resumes here and vice versa (FlatAdam keeps torch.o
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import time
 from typing import Callable, Dict, Optional, Sequence
@@ -45,7 +46,13 @@ class DPTrainStep:
     ``device_guard=True``: the loss-threshold guard (every threshold, GUARD_OFF included: a NaN loss always skips), a skip on
     a non-finite averaged gradient (``skip_nonfinite``) and global-norm clipping (``max_grad_norm``, clip_grad_norm_'s
     rule) are decided on the device; ``step()`` never takes the eager guarded branch and, on one rank, the captured graph
-    holds guard and Adam too.  ``guard_stats()`` / ``checkpoint()`` are the only reads of the step state."""
+    holds guard and Adam too.  ``guard_stats()`` / ``checkpoint()`` are the only reads of the step state.
+    ``ema_decay=d`` (BasicSR / SwinIR: 0.999; ``ema_warmup``: d_t = min(d, (1 + t) / (10 + t))): an exponential moving
+    average of the trainable parameters, updated inside the Adam launch (FlatAdam), so the captured step keeps its one
+    linear chain and gains no launch; a skipped step moves neither the parameters nor the average.  ``ema_scope()``,
+    ``ema_state_dict()``, ``quick_eva()`` and the checkpoint's ``model_g_ema`` read it.  Several ranks need no collective
+    for it: the average is a deterministic function of parameters that are already equal on every rank.  The reference
+    keeps no EMA; it is off by default, and no PSNR gain is claimed for it here (no trained weights, no real volumes)."""
 
     RECORD_FLUSH = 4096   # parked device scalars before they are converted in one batch (bounds the memory they hold)
 
@@ -53,7 +60,8 @@ class DPTrainStep:
                  weight_decay: float = 0.0, milestones: Optional[Sequence[int]] = None, gamma: float = 0.5,
                  loss_threshold: float = GUARD_OFF, loss_fn: Optional[Callable] = None, group=None,
                  graph: bool = False, graph_warmup: int = 2, device_guard: bool = False,
-                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False):
         self.device_guard = bool(device_guard)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.skip_nonfinite = bool(skip_nonfinite)
@@ -66,7 +74,8 @@ class DPTrainStep:
         dp.broadcast_parameters(net, group=group)
         self.bucket = dp.FlatGradBucket(net.parameters())
         self.optimizer = FlatAdam(self.bucket.params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                  bucket=self.bucket, device_state=self.device_guard)
+                                  bucket=self.bucket, device_state=self.device_guard, ema_decay=ema_decay,
+                                  ema_warmup=ema_warmup)
         self.scheduler = (torch.optim.lr_scheduler.MultiStepLR(self.optimizer, milestones=list(milestones), gamma=gamma)
                           if milestones else None)
         if self.device_guard and self.scheduler is not None:
@@ -99,6 +108,13 @@ class DPTrainStep:
         self.current_training_state_id = 0
         self.current_epoch = 0
         self.training_epoch_costs: list = []
+
+    def _refuse_averaged(self, what: str) -> None:
+        """Inside ema_scope() the network holds the averaged weights: gradients of them, or a graph captured with them
+        under it, are never what a training step wants."""
+        if self.optimizer.ema_active:
+            raise RuntimeError(f"DPTrainStep.{what}: inside ema_scope() the network holds the averaged weights; "
+                               "it must not train on them")
 
     def _keep_step(self, loss: torch.Tensor) -> bool:
         """The loss-threshold decision of trans_sr_trainer.py:162, made COLLECTIVELY: every rank must take the same
@@ -170,6 +186,7 @@ class DPTrainStep:
     def fwd_bwd(self, inputs: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
         """forward + loss + backward with the gradients written straight into the flat bucket (no host sync inside:
         capturable).  Returns the loss as a device scalar that is overwritten by the next call."""
+        self._refuse_averaged("fwd_bwd")
         self.bucket.detach_grads()       # autograd assigns fresh gradients; the HIP ops take the bucket views as destinations
         out = self.net(inputs)
         loss = self._loss(out, targets)
@@ -197,7 +214,7 @@ class DPTrainStep:
     def capture(self, inputs: torch.Tensor, targets: torch.Tensor) -> bool:
         """Capture fwd_bwd on (copies of) these tensors into a HIP graph.  False (and eager from then on) if the capture
         fails; the parameters and BatchNorm statistics are not touched by a failed capture."""
-        import contextlib
+        self._refuse_averaged("capture")   # before the try below: it is a caller's mistake, not a capture that failed
         self._static = (inputs.detach().clone(), targets.detach().clone())
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
@@ -237,6 +254,7 @@ class DPTrainStep:
 
     def step(self, inputs: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
         """One iteration of trans_sr_trainer.py:131-178; returns the (device) loss."""
+        self._refuse_averaged("step")                  # a replayed graph would not pass FlatAdam.step's own check
         t0 = time.time()                               # :132
         self.current_epoch += 1                        # :134 — advanced whether or not the update is skipped
         self.net.train()
@@ -300,7 +318,7 @@ class DPTrainStep:
 
     def quick_eva(self, lr: torch.Tensor, hr: torch.Tensor, sr_scale: Optional[float] = None, metrics: str = "psnr ssim",
                   num_samples: int = 64, batch_size: int = 16, generator: Optional[torch.Generator] = None,
-                  return_mode: str = "mean") -> dict:
+                  return_mode: str = "mean", use_ema: Optional[bool] = None) -> dict:
         """The quick validation of models/basic_trainer.py:257-286 (run every ``check_every`` iterations,
         trans_sr_trainer.py:180-181) on validation slices the caller loaded: ``num_samples`` random slices of ``lr`` (N, C, h, w)
         / ``hr`` (N, C, h*s, w*s) (torch.randperm with ``generator``; the reference shuffles with numpy) are super-resolved as
@@ -308,9 +326,18 @@ class DPTrainStep:
         GPU (metrics.device_scores) after cropping ceil(s) border pixels.  The report, keyed as MetaSREvaluation keys it
         (``psnr_4.0``, metrics/sr_evaluation.py:142-156), is appended to ``quick_validation_reports`` and returned.
         The optimizer, the gradient bucket, the loss records, the packed weights and a captured graph are left as they were:
-        the next step() computes what it would have computed without this call."""
+        the next step() computes what it would have computed without this call.
+        ``use_ema``: None = the averaged weights when the trainer keeps an EMA, False = the live weights, True without an EMA
+        raises.  The averaged weights are put under the network by ``ema_scope()`` (an in-place exchange) and taken out again
+        before this returns, so the promise above holds for them too."""
         from . import ops
         from .metrics import SRMetrics
+        if use_ema and not self.ema_enabled:
+            raise RuntimeError("DPTrainStep.quick_eva(use_ema=True): needs DPTrainStep(ema_decay=...)")
+        want_ema = self.ema_enabled if use_ema is None else bool(use_ema)
+        if self.ema_enabled and self.optimizer.ema_active and not want_ema:
+            raise RuntimeError("DPTrainStep.quick_eva(use_ema=False) inside ema_scope(): the network holds the averaged weights")
+        scope = self.ema_scope if want_ema and not self.optimizer.ema_active else contextlib.nullcontext
         scorer = SRMetrics(metrics, return_mode, device="cuda")
         s = float(sr_scale if sr_scale is not None else getattr(self.net, "sr_scale", getattr(self.net, "upscale", 1)))
         idx = torch.randperm(len(lr), generator=generator)[:int(num_samples)]
@@ -318,7 +345,7 @@ class DPTrainStep:
         modes = [(m, m.training) for m in self.net.modules()]
         self.net.eval()
         try:
-            with torch.no_grad(), ops.keep_pack_plan(self.net):
+            with torch.no_grad(), ops.keep_pack_plan(self.net), scope():
                 rec = torch.cat([self.net(p.to(dev)) for p in lr[idx.to(lr.device)].split(int(batch_size) * 4)])
         finally:
             for m, t in modes:
@@ -327,6 +354,39 @@ class DPTrainStep:
         report = {f"{m}_{s}": v for m, v in rep.items()}
         self.quick_validation_reports.append(report)
         return report
+
+    # ---- the weight EMA (ema_decay=...) ------------------------------------------------------------------------------
+    @property
+    def ema_enabled(self) -> bool:
+        return self.optimizer.ema is not None
+
+    def ema_scope(self):
+        """``with trainer.ema_scope():`` the network computes from the averaged weights (FlatAdam.ema_scope: one in-place
+        exchange on entry, one on exit, also when the body raises).  No parameter moves, so the pack plan, the trainer's
+        captured graph and an ``SRTester`` graph captured on the live weights stay valid; ``step()`` raises inside."""
+        return self.optimizer.ema_scope()
+
+    def ema_state_dict(self) -> dict:
+        """``net.state_dict()`` (its keys, its order) with every trainable parameter's entry replaced by a clone of its
+        averaged value; buffers and frozen parameters as they are.  Loads strictly into a plain network."""
+        if not self.ema_enabled:
+            raise RuntimeError("DPTrainStep.ema_state_dict: needs DPTrainStep(ema_decay=...)")
+        opt = self.optimizer
+        # inside ema_scope() the buffers are exchanged: the averaged values then sit under the parameters themselves
+        avg = {id(p): (p if opt.ema_active else v) for p, v in zip(opt.param_groups[0]["params"], opt.ema_views())}
+        sd = self.net.state_dict()
+        for name, p in self.net.named_parameters():
+            if id(p) in avg:
+                sd[name] = avg[id(p)].detach().clone()
+        return sd
+
+    def _load_ema(self, sd: dict) -> None:
+        opt = self.optimizer
+        views = {id(p): v for p, v in zip(opt.param_groups[0]["params"], opt.ema_views())}
+        with torch.no_grad():
+            for name, p in self.net.named_parameters():
+                if id(p) in views:
+                    views[id(p)].copy_(sd[name])
 
     def _collective(self) -> bool:
         return (dist.is_available() and dist.is_initialized()
@@ -364,6 +424,10 @@ class DPTrainStep:
 
     # ---- models/basic_trainer.py:164-208 -----------------------------------------------------------
     def checkpoint(self) -> dict:
+        """The reference's keys.  A trainer with an EMA adds two: ``model_g_ema`` (``ema_state_dict()``) and ``ema``
+        (``{"decay", "warmup"}``); without one the keys are exactly the reference's."""
+        if self.ema_enabled and self.optimizer.ema_active:
+            raise RuntimeError("DPTrainStep.checkpoint: inside ema_scope() 'model_g' would hold the averaged weights")
         self._flush_records()
         if self.device_guard:
             self.optimizer.sync_host()                 # step count, rate and scheduler fields as `kept` updates leave them
@@ -379,16 +443,29 @@ class DPTrainStep:
               "training_epoch_costs": self.training_epoch_costs}
         if self.scheduler is not None:
             ck["scheduler_g"] = self.scheduler.state_dict()
+        if self.ema_enabled:
+            ck["model_g_ema"] = self.ema_state_dict()
+            ck["ema"] = {"decay": self.optimizer.ema_decay, "warmup": self.optimizer.ema_warmup}
         return ck
 
     def save_checkpoint(self, path: str) -> None:
         torch.save(self.checkpoint(), path)
 
     def load_checkpoint(self, path_or_dict, map_location=None) -> None:
+        """With an EMA, ``model_g_ema`` is loaded into the averaged buffer when the checkpoint has it; when it has not (a
+        reference checkpoint, or one written without an EMA) the average restarts from the loaded parameters
+        (``reset_ema()``).  The decay stays the constructor's.  A trainer without an EMA ignores both keys."""
         ck = path_or_dict if isinstance(path_or_dict, dict) else torch.load(path_or_dict, map_location=map_location,
                                                                             weights_only=False)
+        if self.ema_enabled and self.optimizer.ema_active:
+            raise RuntimeError("DPTrainStep.load_checkpoint: inside ema_scope()")
         # parameters are views of the optimizer's flat buffer: load_state_dict copies in place and keeps them
         self.net.load_state_dict(ck["model_g"])
+        if self.ema_enabled:
+            if "model_g_ema" in ck:
+                self._load_ema(ck["model_g_ema"])
+            else:
+                self.optimizer.reset_ema()
         self.optimizer.load_state_dict(ck["optimizer_g"])
         if self.scheduler is not None and "scheduler_g" in ck:
             self.scheduler.load_state_dict(ck["scheduler_g"])
