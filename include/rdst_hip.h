@@ -139,8 +139,9 @@ int rdst_ln_linear_fwd(const void* X, int64_t ld_x, const float* ln_w, const flo
 /* Backward of rdst_ln_linear_fwd.  dY (M,N) -> dX (M,K) = dX_add + f'(...) where dX_add is an optional
  * (M,K) tensor added on the way out (NULL = none; it may alias dX for an in-place accumulate) - this is how
  * the gradient of a residual fan-out is summed without a separate add kernel; dW (N,K), dbias (N),
- * dln_w/dln_b (K) [overwritten; any of them may be NULL to skip].  The gradient of the forward's residual
- * operand R is dY itself and is the caller's business. */
+ * dln_w/dln_b (K) [overwritten; any of them may be NULL to skip].  dX may be NULL too (a frozen input: dX_add is
+ * then ignored); every combination of NULL outputs is served, d(gamma) / d(beta) without dX included, and none returns
+ * RDST_ENOTSUP.  The gradient of the forward's residual operand R is dY itself and is the caller's business. */
 size_t rdst_ln_linear_bwd_workspace(int64_t M, int K, int N);
 int rdst_ln_linear_bwd(const void* X, int64_t ld_x, const float* ln_w, const float* ln_b,
                        const float* stats, int in_act, const float* Wt, const void* dY,
@@ -210,7 +211,8 @@ int rdst_conv_fwd(const void* X, int64_t ld_x, int in_act, const float* Wc, cons
                   void* stream);
 
 /* Backward: dY (output geometry) -> dX (B*H*W, Cin) = dX_add + ... (dX_add optional, may alias dX),
- * dW (Cout,Cin,k,k), dbias (Cout) [overwritten; may be NULL]. */
+ * dW (Cout,Cin,k,k), dbias (Cout) [overwritten; may be NULL].  dX may be NULL too (the head conv: its input is the
+ * image); every non-empty subset of (dX, dW, dbias) is served. */
 size_t rdst_conv_bwd_workspace(int B, int H, int W, int Cin, int Cout, int ksize);
 int rdst_conv_bwd(const void* X, int64_t ld_x, int in_act, const float* Wc, const void* dY,
                   int64_t ld_dy, void* dX, int64_t ld_dx, const void* dX_add, int64_t ld_dx_add, float* dW,

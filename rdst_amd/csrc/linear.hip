@@ -556,7 +556,9 @@ int bwd_t(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, const f
       }
       if (rc != RDST_ENOTSUP) return rc;
     }
-    if (dX) {
+    // behind a LayerNorm, d(gamma) / d(beta) need dA = s dY W as much as dX does (a frozen input in front of a trainable norm):
+    // the row kernel below reads it whether or not dX is wanted
+    if (dX || (ln_w && (dln_w || dln_b))) {
       int rc = linear_dgrad_mfma<T>(X, ldx, ln_w != nullptr, in_act, Wt, dY, lddy, dX, lddx, acc, ldacc, dA, M, K, N, s, split, st);
       if (rc == RDST_ENOTSUP) {
         DyA<T> la{dY, lddy, s};

@@ -15,6 +15,9 @@ decoded job table.  ``plan:`` lines give the module's PackPlan after a forward. 
 Not covered here: the ``g.is_cuda`` branch of _DenseJoin.backward (the layer's outer reduction batch does not open on CPU
 tensors; one scenario opens a batch by hand instead) and real refusals by the kernels.  The GPU suite covers both:
 test_grad_accum_gpu.py, test_mlp_gpu.py::test_swin_block_backward_with_misaligned_gradient, test_lnlin3_gpu.py.
+The stand-in answers 0 and writes nothing, so the frozen-parameter scenarios pin only WHICH calls are made (and with which
+NULL outputs); what those calls compute is checked in test_partial_grads_gpu.py, which runs the same freeze patterns through
+ops.swin_block and every NULL pattern of rdst_ln_linear_bwd / rdst_conv_bwd on the device against float64 autograd.
 
     python tests/test_ops_trace.py --record   # rewrite the trace from the rdst_amd/ops.py in the tree
 """

@@ -175,3 +175,151 @@ def local_rel(got, want, tiles):
         idx.append(i % g)
         i //= g
     return rel.max().item(), rel.median().item(), tuple(reversed(idx))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Partial gradient requests (test_partial_grads_gpu.py / test_partial_grads_host.py): the request masks, the float64
+# reference, the "wide" row layout and the guarded workspace.
+# ---------------------------------------------------------------------------------------------------------------------
+ACT_NONE, ACT_GELU, ACT_LEAKY02 = 0, 1, 2
+
+# masks over (dX, dW, dbias, dln_w, dln_b) of rdst_ln_linear_bwd behind a LayerNorm
+LIN_MASKS_LN = {
+    "all": (1, 1, 1, 1, 1),
+    "dx": (1, 0, 0, 0, 0),
+    "dw+db": (0, 1, 1, 0, 0),
+    "dw": (0, 1, 0, 0, 0),
+    "db": (0, 0, 1, 0, 0),
+    "dx+dw+dlw+dlb": (1, 1, 0, 1, 1),      # a bias-free Linear
+    "dx+dlw+dlb": (1, 0, 0, 1, 1),         # frozen Linear
+    "dlw+dlb": (0, 0, 0, 1, 1),
+    "dx+dw+db": (1, 1, 1, 0, 0),           # frozen LayerNorm
+    "dlw": (0, 0, 0, 1, 0),
+    "dlb": (0, 0, 0, 0, 1),
+    "dx+db": (1, 0, 1, 0, 0),
+}
+# ... without a LayerNorm (dln_w / dln_b do not exist)
+LIN_MASKS_PLAIN = {
+    "all": (1, 1, 1, 0, 0),
+    "dx": (1, 0, 0, 0, 0),
+    "dw+db": (0, 1, 1, 0, 0),
+    "dw": (0, 1, 0, 0, 0),
+    "db": (0, 0, 1, 0, 0),
+    "dx+dw": (1, 1, 0, 0, 0),
+    "dx+db": (1, 0, 1, 0, 0),
+}
+# ... LayerNorm only (Wt == NULL): every non-empty subset of (dX, dln_w, dln_b)
+LN_ONLY_MASKS = {
+    "+".join(n for n, f in zip(("dx", "dlw", "dlb"), (a, b, c)) if f): (a, 0, 0, b, c)
+    for a in (0, 1) for b in (0, 1) for c in (0, 1) if a or b or c
+}
+# masks over (dX, dW, dbias) of rdst_conv_bwd: all seven non-empty subsets
+CONV_MASKS = {
+    "+".join(n for n, f in zip(("dx", "dw", "db"), (a, b, c)) if f): (a, b, c)
+    for a in (0, 1) for b in (0, 1) for c in (0, 1) if a or b or c
+}
+
+
+def _act64(h, act):
+    import torch.nn.functional as F
+    if act == ACT_GELU:
+        return O.gelu(h)
+    if act == ACT_LEAKY02:
+        return F.leaky_relu(h, 0.2)
+    if act != ACT_NONE:
+        raise ValueError(f"activation code {act}")
+    return h
+
+
+def linear_bwd_ref(x, ln_w, ln_b, w, b, gy, act, scale, add=None, dtype=torch.float64):
+    """Every gradient of Y = (f(X) @ W^T + b) * scale for the upstream gradient gy, by torch autograd in `dtype`
+    (float64: the reference of the GPU tests): f = LayerNorm (ln_w given), the activation `act`, or identity; w None =
+    LayerNorm only.  `add` is dX_add: dX = add + f'(...).  Returns {"dx", "dw", "db", "dlw", "dlb"} (None where the
+    operand does not exist); the inputs are left unchanged."""
+    import torch.nn.functional as F
+
+    def leaf(t):
+        return None if t is None else t.detach().to(dtype).clone().requires_grad_(True)
+    xr, lw, lb, wr, br = leaf(x), leaf(ln_w), leaf(ln_b), leaf(w), leaf(b)
+    h = F.layer_norm(xr, (xr.shape[-1],), lw, lb, 1e-5) if lw is not None else _act64(xr, act)
+    if wr is not None:
+        h = F.linear(h, wr, br)
+    (h * scale).backward(gy.detach().to(dtype))
+    dx = xr.grad if add is None else xr.grad + add.detach().to(dtype)
+
+    def grad(t):
+        return None if t is None else t.grad
+    return {"dx": dx, "dw": grad(wr), "db": grad(br), "dlw": grad(lw), "dlb": grad(lb)}
+
+
+def conv_bwd_ref(x, w, b, gy, act, scale, r, add=None, dtype=torch.float64):
+    """Every gradient of the conv on rows: x (B, H, W, Cin), w (Cout, Cin, k, k), gy in the output geometry
+    (B, H r, W r, Cout / r^2) - activation on the input side, zero padding k // 2, * scale, PixelShuffle(r).
+    Returns {"dx", "dw", "db"} in `dtype`, dx token-major like x (+ add)."""
+    import torch.nn.functional as F
+    xr = x.detach().to(dtype).clone().requires_grad_(True)
+    wr = w.detach().to(dtype).clone().requires_grad_(True)
+    br = b.detach().to(dtype).clone().requires_grad_(True)
+    h = F.conv2d(_act64(xr.permute(0, 3, 1, 2), act), wr, br, padding=w.shape[-1] // 2)
+    if r > 1:
+        h = F.pixel_shuffle(h, r)
+    (h.permute(0, 2, 3, 1) * scale).backward(gy.detach().to(dtype))
+    dx = xr.grad if add is None else xr.grad + add.detach().to(dtype)
+    return {"dx": dx, "dw": wr.grad, "db": br.grad}
+
+
+def ln_stats(x):
+    """The forward's LayerNorm statistics (M, 2) {mean, rstd} in fp32, from float64 on the host."""
+    xf = x.detach().double()
+    return torch.stack([xf.mean(-1), (xf.var(-1, unbiased=False) + 1e-5).rsqrt()], 1).float().contiguous()
+
+
+_INT_OF = {2: torch.int16, 4: torch.int32}
+WIDE_FILL = {2: 0x4B4D, 4: 0x4B4D4B4D}      # the (finite) bit pattern of every element outside the slice
+# (byte offset of the slice, leading dimension in bytes mod 16) per operand slot: every row starts on a 4-byte
+# boundary and none on a 16-byte one (offset 8 with rows 0 mod 16: always 8; offset 4 or 12 with rows 8 mod 16: 4, 12, 4 ...)
+WIDE_SLOTS = {"x": (8, 0), "dy": (4, 8), "dx": (8, 0), "add": (12, 8)}
+
+
+class Wide:
+    """A (rows, cols) matrix as a column slice of a wider buffer (rows, ld): `view` is the slice (write the operand into
+    it, hand `view.data_ptr()` and `ld` to the kernel), `intact()` says whether every element OUTSIDE the slice still
+    holds its fill pattern, bit for bit."""
+
+    def __init__(self, rows, cols, dtype, slot, device="cpu"):
+        elt = torch.empty((), dtype=dtype).element_size()
+        off_b, mod16 = WIDE_SLOTS[slot]
+        self.off = off_b // elt
+        ld = self.off + cols + 4 // elt
+        while (ld * elt) % 16 != mod16:
+            ld += 1
+        self.ld, self.cols, self.elt = ld, cols, elt
+        self.buf = torch.full((rows, ld), WIDE_FILL[elt], dtype=_INT_OF[elt], device=device).view(dtype)
+        self.view = self.buf[:, self.off:self.off + cols]
+        for r in range(min(rows, 4)):   # the layout the tests ask for
+            a = self.off * elt + r * ld * elt
+            assert a % 4 == 0 and a % 16 != 0, (slot, cols, dtype)
+
+    def intact(self):
+        bits = self.buf.view(_INT_OF[self.elt])
+        fill = torch.full_like(bits[:, :1], WIDE_FILL[self.elt])
+        left, right = bits[:, :self.off], bits[:, self.off + self.cols:]
+        return bool((left == fill).all()) and bool((right == fill).all())
+
+
+class GuardedWorkspace:
+    """`nbytes` of scratch as the middle of a larger allocation: 4096 sentinel bytes on either side (the second starts at
+    byte `nbytes` exactly), the scratch itself filled with 0xFF (fp32 NaN: a kernel that reads scratch nobody wrote shows)."""
+    GUARD, SENTINEL = 4096, 0xA5
+
+    def __init__(self, nbytes, device="cpu"):
+        self.nbytes = int(nbytes)
+        self.buf = torch.full((2 * self.GUARD + self.nbytes,), self.SENTINEL, dtype=torch.uint8, device=device)
+        self.buf[self.GUARD:self.GUARD + self.nbytes] = 0xFF
+
+    def ptr(self):
+        return self.buf.data_ptr() + self.GUARD
+
+    def intact(self):
+        lo, hi = self.buf[:self.GUARD], self.buf[self.GUARD + self.nbytes:]
+        return bool((lo == self.SENTINEL).all()) and bool((hi == self.SENTINEL).all())
