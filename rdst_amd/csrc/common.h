@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <initializer_list>
 #include "../../include/rdst_hip.h"
 
 typedef __hip_bfloat16 bf16;
@@ -14,14 +15,18 @@ typedef __hip_bfloat16 bf16;
 // constant 0 and rdst_dbg_getenv() a constant null pointer, so every `if (RDST_DBGV(p.dbg) & 2)` /
 // `if (RDST_DBGV(p.stamps) && ...)` branch and every `e ? atoi(e) : dflt` folds away at compile time: no
 // getenv, hipMalloc or host sync in a launcher, no ablation test inside a kernel loop.
+enum { RDST_STAMPS_SUMS = 0, RDST_STAMPS_TICKS = 1 };   // what a kernel keeps in its stamp slots: rdst_stamps_end()
 #ifdef RDST_DEBUG
 #include <stdlib.h>
 #define RDST_DBGV(x) (x)
 static inline const char* rdst_dbg_getenv(const char* name) { return getenv(name); }
-// per-workgroup cycle counters of a kernel (debug build only): `env`=N arms the next N launches; the launcher passes
-// the returned device buffer ([grid][n] u64, zeroed) to the kernel and calls rdst_stamps_end() after the launch, which
-// synchronises, averages every slot over the workgroups and prints it.
-static inline unsigned long long* rdst_stamps_begin(const char* env, int grid, int n, hipStream_t st) {
+// per-workgroup cycle counters of a kernel (debug build only): while `env` is set to a positive number every launch is
+// armed; the launcher passes the returned device buffer ([grid][n] u64, zeroed) to the kernel and calls rdst_stamps_end()
+// after the launch, which synchronises and prints one summary over the workgroups, headed by the printf-style tag.
+//   RDST_STAMPS_SUMS   the kernel ACCUMULATES cycles in its slots (RDST_PHASES_*): the mean of every slot
+//   RDST_STAMPS_TICKS  the kernel writes the cycle counter itself into slot after slot (0 = never reached): per slot, over
+//                      the workgroups that reached it, the mean distance to the slot before it and to slot 0
+static inline unsigned long long* rdst_stamps_begin(const char* env, int64_t grid, int n, hipStream_t st) {
   const char* e = getenv(env);
   if (!e || atoi(e) <= 0) return nullptr;
   unsigned long long* d = nullptr;
@@ -29,27 +34,45 @@ static inline unsigned long long* rdst_stamps_begin(const char* env, int grid, i
   (void)hipMemsetAsync(d, 0, (size_t)grid * n * 8, st);
   return d;
 }
-static inline void rdst_stamps_end(const char* tag, unsigned long long* d, int grid, int n, hipStream_t st) {
+template <class... A>
+static inline void rdst_stamps_end(unsigned long long* d, int64_t grid, int n, int mode, hipStream_t st, const char* tag, const A&... a) {
   if (!d) return;
   (void)hipStreamSynchronize(st);
   unsigned long long* h = (unsigned long long*)malloc((size_t)grid * n * 8);
   (void)hipMemcpy(h, d, (size_t)grid * n * 8, hipMemcpyDeviceToHost);
   (void)hipFree(d);
-  fprintf(stderr, "[stamps %s grid=%d] mean cycles per workgroup:", tag, grid);
+  fprintf(stderr, "[stamps ");
+  fprintf(stderr, tag, a...);
+  fprintf(stderr, " grid=%lld] %s\n", (long long)grid,
+          mode == RDST_STAMPS_TICKS ? "mean ticks since the stamp before / since stamp 0 (n workgroups)" : "mean cycles per workgroup");
   for (int k = 0; k < n; ++k) {
-    double sum = 0;
-    for (int w = 0; w < grid; ++w) sum += (double)h[(size_t)w * n + k];
-    fprintf(stderr, " %d:%.0f", k, sum / grid);
+    double sum = 0, sum0 = 0;
+    int cnt = 0;
+    for (int64_t w = 0; w < grid; ++w) {
+      const unsigned long long* s = h + (size_t)w * n;
+      if (mode == RDST_STAMPS_TICKS && !s[k]) continue;
+      sum += (double)(mode == RDST_STAMPS_TICKS ? s[k] - s[k ? k - 1 : 0] : s[k]);
+      sum0 += (double)(s[k] - s[0]);
+      cnt++;
+    }
+    if (!cnt) continue;
+    if (mode == RDST_STAMPS_TICKS) fprintf(stderr, "  %2d: %9.0f %9.0f (n=%d)\n", k, sum / cnt, sum0 / cnt, cnt);
+    else fprintf(stderr, "  %2d: %9.0f\n", k, sum / cnt);
   }
-  fprintf(stderr, "\n");
   free(h);
 }
 #else
 #define RDST_DBGV(x) 0
 static inline constexpr const char* rdst_dbg_getenv(const char*) { return nullptr; }
-static inline unsigned long long* rdst_stamps_begin(const char*, int, int, hipStream_t) { return nullptr; }
-static inline void rdst_stamps_end(const char*, unsigned long long*, int, int, hipStream_t) {}
+static inline unsigned long long* rdst_stamps_begin(const char*, int64_t, int, hipStream_t) { return nullptr; }
+template <class... A>
+static inline void rdst_stamps_end(unsigned long long*, int64_t, int, int, hipStream_t, const char*, const A&...) {}
 #endif
+// RDST_DISABLE_MFMA=1 (debug build): every matrix-core launcher passes and the generic kernels serve
+static inline bool mfma_disabled() {
+  const char* e = rdst_dbg_getenv("RDST_DISABLE_MFMA");
+  return e && e[0] == '1';
+}
 
 // The kernel side of the stamps: where a kernel's time goes, phase by phase.  Both fold to nothing when they are off.
 // RDST_PHASES_BEGIN(on) declares 8 cycle counters; RDST_PHASE(on, k) adds the cycles since the previous RDST_PHASE to counter k;
@@ -119,6 +142,23 @@ static inline int rdst_launch(K kern, dim3 grid, dim3 threads, size_t smem, hipS
   if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   hipLaunchKernelGGL(kern, grid, threads, smem, st, args...);
   return rdst_launch_status(what);
+}
+
+// Every pointer and every leading dimension (in BYTES) is a multiple of the granule `gran` (a kernel's chunk size).
+static inline bool rdst_aligned(int gran, std::initializer_list<const void*> ptrs, std::initializer_list<int64_t> ld_bytes) {
+  for (const void* q : ptrs)
+    if ((uintptr_t)q % gran) return false;
+  for (int64_t l : ld_bytes)
+    if (l % gran) return false;
+  return true;
+}
+
+// The persistent grid plan: `ntiles` tiles over at most `cap` workgroups, each taking *tiles_per_wg consecutive tiles, and
+// no more workgroups than that leaves with work.  Returns the grid.
+static inline int64_t rdst_tile_grid(int64_t ntiles, int64_t cap, int* tiles_per_wg) {
+  const int64_t grid = ntiles < cap ? ntiles : cap;
+  *tiles_per_wg = (int)((ntiles + grid - 1) / grid);
+  return (ntiles + *tiles_per_wg - 1) / *tiles_per_wg;
 }
 
 // The compute mode of an entry point's dtype, decoded first thing: `dtype` becomes the element type of the rows (RDST_BF16 or

@@ -525,7 +525,7 @@ int launch_c3(C3Args<AR>& p, int ctile0, hipStream_t st, const char* what) {
   auto kern = conv3_kernel<AR, K, CW, NT, KSPLIT, PSLOTS, RPS, UNSHUF, PSTORE>;
   p.stamps = rdst_stamps_begin(AR::STAMPS, grid, 8, st);
   const int rc = rdst_launch(kern, dim3((unsigned)grid), dim3(256), CF::SMEM, st, what, p);
-  rdst_stamps_end(what, p.stamps, grid, 8, st);   // 0 weights, 1 first rows, 2 dma issue, 3 mfma, 4 exchange, 5 epilogue, 6 barrier
+  rdst_stamps_end(p.stamps, grid, 8, RDST_STAMPS_SUMS, st, "%s", what);   // 0 weights, 1 first rows, 2 dma issue, 3 mfma, 4 exchange, 5 epilogue, 6 barrier
   return rc;
 }
 

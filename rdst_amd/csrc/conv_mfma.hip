@@ -15,21 +15,11 @@
 // of dY and of the three kx-shifted input rows are staged in LDS and read transposed
 // (ds_read_b64_tr_b16) / element-wise (fp32).  d(bias) rides on a ones column of the centre tap.
 #include "conv.h"
+#include "gemm_valu.h"   // slab_reduce
 #include "mfma.h"
 #include <stdlib.h>
 
-int slab_reduce(const float* slab, float* out, int S, int64_t n, hipStream_t st);
-
 namespace {
-
-bool mfma_disabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = rdst_dbg_getenv("RDST_DISABLE_MFMA");
-    v = (e && e[0] == '1') ? 1 : 0;
-  }
-  return v == 1;
-}
 
 constexpr int CMODE_FWD = 0, CMODE_DGRAD = 1;
 constexpr int CV_MAXCT = 3;  // column tiles per chunk (96 output channels)

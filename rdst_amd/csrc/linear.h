@@ -43,11 +43,16 @@ int wgrad_ln_finish_launch(const float* G, const float* Wt, const float* ln_w, c
                            float* dW, float* dbias, float* dln_w, float* dln_b, hipStream_t st);
 int wgrad_sum_launch(const float* slab, int nwg, int tot, float* G, hipStream_t st);
 int wgrad_reduce_launch(const float* slab, int nwg, int N, int K, float s, float* dW, float* dbias, hipStream_t st);
-// LayerNorm + Linear backward (dX, dW, dbias, d(gamma), d(beta)) in ONE pass over (x, dY): mlp_mfma.hip
+// LayerNorm + Linear backward (dX, dW, dbias, d(gamma), d(beta)) in ONE pass over (x, dY): lnlin_mfma.hip, which tries ...
 int linear_ln_bwd_fused_bf16(const bf16* X, int64_t ldx, const float* ln_w, const float* ln_b, const float* stats,
                              const float* Wt, const bf16* dY, int64_t lddy, bf16* dX, int64_t lddx, const bf16* acc,
                              int64_t ldacc, float* dW, float* dbias, float* dln_w, float* dln_b, float* slab, float* G,
                              int64_t M, int K, int N, float s, hipStream_t st, const bf16* acc2 = nullptr, int64_t ldacc2 = 0);
+// ... its re-cut for the E1 shapes first (lnlin3_mfma.hip): dX and the per-workgroup bf16 G4 slabs (*grid_out of them, at
+// most max_wgs) for the caller to reduce; RDST_ENOTSUP for everything else
+int lnlin3_bwd_bf16(const bf16* X, int64_t ldx, const float* ln_w, const float* stats, const float* Wt, const bf16* dY,
+                    int64_t lddy, bf16* dX, int64_t lddx, const bf16* acc, int64_t ldacc, const bf16* acc2, int64_t ldacc2,
+                    float* slab, int64_t slab_stride, int64_t M, int K, int N, int64_t max_wgs, int* grid_out, hipStream_t st);
 
 // streaming forward for the E1 shapes, bf16 (lin3_mfma.hip); RDST_ENOTSUP for everything else.
 // wpack: lin3_pack_bytes(K, N) bytes of 16-byte aligned device scratch (NULL -> RDST_ENOTSUP).

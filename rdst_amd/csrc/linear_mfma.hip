@@ -22,15 +22,6 @@
 
 namespace {
 
-bool mfma_disabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = rdst_dbg_getenv("RDST_DISABLE_MFMA");
-    v = (e && e[0] == '1') ? 1 : 0;
-  }
-  return v == 1;
-}
-
 constexpr int MODE_FWD = 0, MODE_DGRAD = 1;
 constexpr float kLnEps = 1e-5f;
 
@@ -752,13 +743,7 @@ int launch_lin(LinArgs<T>& p, bool split, hipStream_t st, const char* what) {
   int64_t cap = 256;  // persistent: one 8-wave workgroup per CU (the kernel's register count admits no second one)
   { const char* e = rdst_dbg_getenv("RDST_LIN_GRID"); if (e && atoi(e) > 0) cap = atoi(e); }
   if (grid > cap) grid = cap;
-  static int want_stamps = -1;
-  if (want_stamps < 0) { const char* e = rdst_dbg_getenv("RDST_LIN_STAMPS"); want_stamps = e ? atoi(e) : 0; }
-  unsigned long long* hst = nullptr;
-  if (want_stamps > 0) {
-    (void)hipMalloc((void**)&p.stamps, (size_t)grid * 16 * 8);
-    (void)hipMemsetAsync(p.stamps, 0, (size_t)grid * 16 * 8, st);
-  }
+  p.stamps = rdst_stamps_begin("RDST_LIN_STAMPS", grid, 16, st);
   int rc = 0;
 #define RDST_LIN_LAUNCH(TM)                                                                                          \
   {                                                                                                                  \
@@ -769,23 +754,7 @@ int launch_lin(LinArgs<T>& p, bool split, hipStream_t st, const char* what) {
   }
   if (p.Tn <= 8) RDST_LIN_LAUNCH(8) else if (p.Tn <= 16) RDST_LIN_LAUNCH(16) else RDST_LIN_LAUNCH(32)
 #undef RDST_LIN_LAUNCH
-  if (want_stamps > 0) {
-    (void)hipStreamSynchronize(st);
-    hst = (unsigned long long*)malloc((size_t)grid * 16 * 8);
-    (void)hipMemcpy(hst, p.stamps, (size_t)grid * 16 * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(p.stamps);
-    if (--want_stamps == 0) {
-      double sum[16] = {0}; int cnt[16] = {0};
-      for (int64_t w = 0; w < grid; ++w)
-        for (int k = 1; k < 16; ++k) {
-          if (!hst[w * 16 + k]) continue;
-          sum[k] += (double)(hst[w * 16 + k] - hst[w * 16 + k - 1]); cnt[k]++;
-        }
-      fprintf(stderr, "[lin stamps %s Kc=%d Nout=%d grid=%lld] mean ticks between consecutive stamps\n", what, p.Kc, p.Nout, (long long)grid);
-      for (int k = 1; k < 16; ++k) if (cnt[k]) fprintf(stderr, "  %2d: %9.0f (n=%d)\n", k, sum[k] / cnt[k], cnt[k]);
-    }
-    free(hst);
-  }
+  rdst_stamps_end(p.stamps, grid, 16, RDST_STAMPS_TICKS, st, "%s Kc=%d Nout=%d", what, p.Kc, p.Nout);
   return rc;
 }
 
@@ -1339,7 +1308,7 @@ int wgrad_sum_launch(const float* slab, int nwg, int tot, float* G, hipStream_t 
   j.slab = slab; j.nwg = nwg; j.stride = tot; j.tot = tot; j.map = rbatch::MAP_COPY; j.out = G;
   return rbatch::sum(j, st);
 }
-// launcher of the LayerNorm finish for other translation units (mlp_mfma.hip)
+// launcher of the LayerNorm finish for other translation units (mlp_mfma.hip, lnlin_mfma.hip)
 int wgrad_ln_finish_launch(const float* G, const float* Wt, const float* ln_w, const float* ln_b, int N, int K, float s,
                            float* dW, float* dbias, float* dln_w, float* dln_b, hipStream_t st) {
   rbatch::FinJob j{};
@@ -1403,7 +1372,6 @@ int linear_dgrad_ln_mfma(const T* X, int64_t ldx, const float* stats, const floa
   return rc;
 }
 
-int linear_wgrad_max_wgs(int N);
 size_t linear_wgrad_mfma_slab_floats(int64_t M, int K, int N) {
   (void)M;
   // 256 workgroups, or up to 1024 small ones for the narrow projections (linear_ln_bwd_fused_bf16)
@@ -1440,10 +1408,9 @@ int wgrad_impl(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, co
   p.ldk = stride(p.KT * 32);
   const size_t smem = (size_t)2 * WG_STRIPE * (p.ldn + p.ldk) + (size_t)2 * p.KT * 32 * sizeof(float);
   if (smem > 160 * 1024) return RDST_ENOTSUP;
-  int64_t nwg = (M + WG_STRIPE - 1) / WG_STRIPE;
-  if (nwg > 256) nwg = 256;
-  p.rows_per_wg = (((M + nwg - 1) / nwg + WG_STRIPE - 1) / WG_STRIPE) * WG_STRIPE;
-  nwg = (M + p.rows_per_wg - 1) / p.rows_per_wg;
+  int stripes_per_wg;
+  const int64_t nwg = rdst_tile_grid((M + WG_STRIPE - 1) / WG_STRIPE, 256, &stripes_per_wg);
+  p.rows_per_wg = (int64_t)stripes_per_wg * WG_STRIPE;
   constexpr int PF = sizeof(T) == 2 ? 2 : 1;  // register sets of prefetched stripes
   const int xf = lnfin ? 4 : ln_w ? 1 : in_act == RDST_ACT_GELU ? 2 : in_act ? 3 : 0;
   // plan size: packs per stripe over 512 threads (bf16 only; the fp32 parity mode keeps the general plan)

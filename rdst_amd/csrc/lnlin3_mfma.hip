@@ -1,5 +1,5 @@
 // Backward of a (LayerNorm-fused) Linear in ONE pass over (x, dY), re-cut for the E1 shapes (K in {60, 90, 120};
-// N = 3K behind norm1, N = K for proj, N = 30 for the dense tails): the round-1 kernel (mlp_mfma.hip:lnlin_bwd_kernel)
+// N = 3K behind norm1, N = K for proj, N = 30 for the dense tails): the round-1 kernel (lnlin_mfma.hip:lnlin_bwd_kernel)
 // ran the weight-gradient product on all waves, THEN the data-gradient product on K/32 of them, with the W.gamma image
 // (up to 110 KB) in LDS, single-buffered tiles and three or four barriers per 32-token tile.  Here
 //   * waves are SPECIALISED: weight-gradient waves own a block of TN x TC accumulator tiles of G = dY^T.x-hat for the
@@ -433,9 +433,7 @@ int lb3_launch(LB3Args& p, int64_t max_wgs, int* grid_out, hipStream_t st) {
   if (percu_env > 0 && percu_env < per_cu) per_cu = percu_env;
   int64_t cap = 256 * (int64_t)per_cu;
   if (cap > max_wgs) cap = max_wgs;
-  int64_t grid = p.ntiles < cap ? p.ntiles : cap;
-  p.tiles_per_wg = (int)((p.ntiles + grid - 1) / grid);
-  grid = (p.ntiles + p.tiles_per_wg - 1) / p.tiles_per_wg;
+  const int64_t grid = rdst_tile_grid(p.ntiles, cap, &p.tiles_per_wg);
   *grid_out = (int)grid;
   return rdst_launch(kern, dim3((unsigned)grid), dim3(CF::NT), CF::SMEM, st, "lnlin3_bwd", p);
 }

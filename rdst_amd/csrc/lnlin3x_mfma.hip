@@ -602,9 +602,7 @@ int lbx_launch(LBXArgs& p, int64_t max_wgs, int* grid_out, hipStream_t st) {
   int per_cu = CF::NWV <= 6 && 2 * CF::SMEM <= 160 * 1024 ? 2 : 1;
   int64_t cap = 256 * (int64_t)per_cu;
   if (cap > max_wgs) cap = max_wgs;
-  int64_t grid = p.ntiles < cap ? p.ntiles : cap;
-  p.tiles_per_wg = (int)((p.ntiles + grid - 1) / grid);
-  grid = (p.ntiles + p.tiles_per_wg - 1) / p.tiles_per_wg;
+  const int64_t grid = rdst_tile_grid(p.ntiles, cap, &p.tiles_per_wg);
   p.slab_stride = (int64_t)N * (K + 1);
   *grid_out = (int)grid;
   return rdst_launch(kern, dim3((unsigned)grid), dim3(CF::NT), CF::SMEM, st, "lnlin3x_bwd", p);

@@ -32,6 +32,10 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
 }
 __device__ __forceinline__ float bf16lo(uint32_t w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf16hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
+__device__ __forceinline__ void unpack8(const u32x4_a4& v, float (&f)[8]) {
+  f[0] = bf16lo(v.x); f[1] = bf16hi(v.x); f[2] = bf16lo(v.y); f[3] = bf16hi(v.y);
+  f[4] = bf16lo(v.z); f[5] = bf16hi(v.z); f[6] = bf16lo(v.w); f[7] = bf16hi(v.w);
+}
 
 // SP (float only): the SPLIT arithmetic of the RDST_F32X3 mode — fp32 rows in memory, a matrix operand is a pack of
 // [4 bf16 hi | 4 bf16 lo] (hi = bf16(x), lo = bf16(x - hi): 16 mantissa bits, same 16 bytes as the 4 floats); see Mma<float, true>.

@@ -335,7 +335,7 @@ int launch_m3(M3Args& p, hipStream_t st) {
   auto kern = mlp3_fwd_kernel<C>;
   p.stamps = rdst_stamps_begin("RDST_M3_STAMPS", grid, 8, st);
   const int rc = rdst_launch(kern, dim3((unsigned)grid), dim3(CF::NTHR), CF::SMEM, st, "mlp3_fwd", p);
-  rdst_stamps_end("mlp3_fwd: 0 wait+B0, 1 stats, 2 phase 1, 3 wait+B2, 4 phase 2, 5 B3+issue", p.stamps, grid, 8, st);
+  rdst_stamps_end(p.stamps, grid, 8, RDST_STAMPS_SUMS, st, "mlp3_fwd: 0 wait+B0, 1 stats, 2 phase 1, 3 wait+B2, 4 phase 2, 5 B3+issue");
   return rc;
 }
 

@@ -655,39 +655,15 @@ int launch_sa(SAArgs& p, hipStream_t st) {
   int64_t G = 256 * WGCU;
   if (G > nwin) G = nwin;
   p.G = (int)G;
-#ifdef SA_STAMPS
-  {
-    static int left = -1;
-    if (left < 0) { const char* e = getenv("SA_STAMPS_N"); left = e ? atoi(e) : 0; }
-    if (left > 0) {
-      const size_t n = (size_t)G * SA_NW * 8;
-      (void)hipMalloc((void**)&p.stamps, n * 8);
-      (void)hipMemsetAsync(p.stamps, 0, n * 8, st);
-      const int rc = rdst_launch(kern, dim3((unsigned)G), dim3(SA_NTH), CF::SMEM, st, "swinattn_fwd", p);
-      (void)hipStreamSynchronize(st);
-      unsigned long long* hst = (unsigned long long*)malloc(n * 8);
-      (void)hipMemcpy(hst, p.stamps, n * 8, hipMemcpyDeviceToHost);
-      (void)hipFree(p.stamps);
-      if (--left == 0) {
-        static const char* nm[8] = {"prologue", "wait top", "A work", "wait B1", "B work", "wait B2", "C work", "-"};
-        fprintf(stderr, "[K8 stamps D=%d grid=%d] mean cycles per workgroup over the launch, by wave:\n", D, (int)G);
-        for (int w = 0; w < SA_NW; ++w) {
-          fprintf(stderr, "  wave %2d:", w);
-          for (int k = 0; k < 7; ++k) {
-            double sum = 0;
-            for (int b = 0; b < (int)G; ++b) sum += (double)hst[((size_t)b * SA_NW + w) * 8 + k];
-            fprintf(stderr, " %s %.0f", nm[k], sum / (double)G);
-          }
-          fprintf(stderr, "\n");
-        }
-      }
-      free(hst);
-      return rc;
-    }
-    p.stamps = nullptr;
-  }
+#ifdef SA_STAMPS   // (armed by SA_STAMPS_N > 0, which like every environment switch needs -DRDST_DEBUG as well)
+  p.stamps = rdst_stamps_begin("SA_STAMPS_N", G, SA_NW * 8, st);
 #endif
-  return rdst_launch(kern, dim3((unsigned)G), dim3(SA_NTH), CF::SMEM, st, "swinattn_fwd", p);
+  const int rc = rdst_launch(kern, dim3((unsigned)G), dim3(SA_NTH), CF::SMEM, st, "swinattn_fwd", p);
+#ifdef SA_STAMPS
+  rdst_stamps_end(p.stamps, G, SA_NW * 8, RDST_STAMPS_SUMS, st,
+                  "K8 D=%d: slot = 8 x wave + phase (0 prologue, 1 wait top, 2 A work, 3 wait B1, 4 B work, 5 wait B2, 6 C work)", D);
+#endif
+  return rc;
 }
 
 }  // namespace

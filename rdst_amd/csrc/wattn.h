@@ -66,8 +66,25 @@ int wattn_fwd_generic(const void* qkv, int64_t ld, const float* table, void* out
 int wattn_bwd_generic(const void* qkv, int64_t ld, const float* table, const void* dout, int64_t ldd, void* dqkv,
                       int64_t ldq, float* slab, const WinGeom& g, float scale, int dtype, hipStream_t st);
 
-// gfx950 matrix-core kernels (wattn_mfma.hip): RDST_ENOTSUP when the shape is not covered; split (fp32 rows only): the
-// RDST_F32X3 form of the kernels (common.h)
+// ---- the launchers: each one launches its own kernel or returns RDST_ENOTSUP; which one a call gets is decided by the
+// route tables of wattn_api.hip alone ----
+// the largest row chunk (16, 8 or 4 bytes) that divides a C-wide section of `sec_bytes`, every pointer and every leading
+// dimension (in bytes); 0 if none does
+static inline int wattn_gran(int sec_bytes, std::initializer_list<const void*> ptrs, std::initializer_list<int64_t> ld_bytes) {
+  for (int gs = 16; gs >= 4; gs >>= 1)
+    if (sec_bytes % gs == 0 && rdst_aligned(gs, ptrs, ld_bytes)) return gs;
+  return 0;
+}
+// window groups of the persistent K2 kernels (one slab row each): one per CU, per window and per slab row at most
+static inline int64_t k2_groups(int64_t nwin, int slab_rows) {
+  int64_t G = 256;
+  if (G > nwin) G = nwin;
+  if (G > slab_rows) G = slab_rows;
+  return G;
+}
+
+// the generic matrix-core kernels (wattn_mfma.hip, wattn_bwd_mfma.hip): ws 8, head dim <= 32, C <= 128, no explicit mask; split
+// (fp32 rows only): the RDST_F32X3 form of the kernels (common.h)
 int wattn_fwd_mfma(const void* qkv, int64_t ld, const float* table, void* out, int64_t ldo, const WinGeom& g,
                    float scale, int dtype, bool split, hipStream_t st);
 // K1 specialised for bf16, ws 8, 6 heads of dim 10/15/20 (wattn_mfma_hd.hip); RDST_ENOTSUP otherwise

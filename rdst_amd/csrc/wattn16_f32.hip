@@ -546,7 +546,6 @@ int launch_f16_bwd(const F16Args& p, hipStream_t st) {
   return rdst_launch(kern, dim3((unsigned)(6 * nwin)), dim3(512), smem, st, "wattn16_f32_bwd", p);
 }
 
-bool al(const void* a, int64_t lda_bytes, int gsz) { return (uintptr_t)a % gsz == 0 && lda_bytes % gsz == 0; }
 int f16_align(int d) { return d == 10 ? 8 : d == 15 ? 4 : 16; }
 
 }  // namespace
@@ -559,7 +558,7 @@ int wattn16_fwd_f32(const float* qkv, int64_t ld, const float* table, float* out
   const int d = g.C / 6;
   if (d != 10 && d != 15 && d != 20) return RDST_ENOTSUP;
   const int a = f16_align(d);
-  if (!(al(qkv, ld * 4, a) && al(out, ldo * 4, a))) return RDST_ENOTSUP;
+  if (!rdst_aligned(a, {qkv, out}, {ld * 4, ldo * 4})) return RDST_ENOTSUP;
   F16Args p{};
   p.qkv = qkv; p.ld = ld; p.table = table; p.out = out; p.ldo = ldo; p.g = g; p.scale = scale;
   return d == 10 ? launch_f16_fwd<10>(p, st) : d == 15 ? launch_f16_fwd<15>(p, st) : launch_f16_fwd<20>(p, st);
@@ -574,7 +573,7 @@ int wattn16_bwd_f32(const float* qkv, int64_t ld, const float* table, const floa
   const int d = g.C / 6;
   if (d != 10 && d != 15 && d != 20) return RDST_ENOTSUP;
   const int a = f16_align(d);
-  if (!(al(qkv, ld * 4, a) && al(dout, ldd * 4, a) && al(dqkv, ldq * 4, a))) return RDST_ENOTSUP;
+  if (!rdst_aligned(a, {qkv, dout, dqkv}, {ld * 4, ldd * 4, ldq * 4})) return RDST_ENOTSUP;
   F16Args p{};
   p.qkv = qkv; p.ld = ld; p.table = table; p.dout = dout; p.ldd = ldd; p.dqkv = dqkv; p.ldq = ldq; p.slab = slab; p.g = g;
   p.scale = scale;

@@ -1379,8 +1379,6 @@ int launch_bwd16(const W16Args& p, hipStream_t st) {
   return rdst_launch(kern, dim3((unsigned)(3 * nwin)), dim3(512), smem, st, "wattn16_bwd", p);
 }
 
-bool al(const void* a, int64_t lda_bytes, int gsz) { return (uintptr_t)a % gsz == 0 && lda_bytes % gsz == 0; }
-
 }  // namespace
 
 // bf16, ws 16, 6 heads of dim 10 / 15 / 20, no explicit mask, scale > 0; RDST_ENOTSUP otherwise
@@ -1392,9 +1390,10 @@ int wattn16_fwd_mfma(const void* qkv, int64_t ld, const float* table, void* out,
   p.qkv = (const bf16*)qkv; p.ld = ld; p.table = table; p.out = (bf16*)out; p.ldo = ldo; p.g = g; p.scale = scale;
   p.nlse_out = nlse;
   const int d = g.C / 6;
-  if (d == 10 && al(qkv, ld * 2, 8) && al(out, ldo * 2, 8)) return launch_fwd16<10>(p, st);
-  if (d == 15 && al(qkv, ld * 2, 4) && al(out, ldo * 2, 4)) return launch_fwd16<15>(p, st);
-  if (d == 20 && al(qkv, ld * 2, 16) && al(out, ldo * 2, 16)) return launch_fwd16<20>(p, st);
+  const auto aligned = [&](int gran) { return rdst_aligned(gran, {qkv, out}, {ld * 2, ldo * 2}); };
+  if (d == 10 && aligned(8)) return launch_fwd16<10>(p, st);
+  if (d == 15 && aligned(4)) return launch_fwd16<15>(p, st);
+  if (d == 20 && aligned(16)) return launch_fwd16<20>(p, st);
   return RDST_ENOTSUP;
 }
 
@@ -1409,12 +1408,12 @@ int wattn16_bwd_mfma(const void* qkv, int64_t ld, const float* table, const void
   p.qkv = (const bf16*)qkv; p.ld = ld; p.table = table; p.dout = (const bf16*)dout; p.ldd = ldd;
   p.dqkv = (bf16*)dqkv; p.ldq = ldq; p.slab = slab; p.g = g; p.scale = scale;
   p.o = (const bf16*)o; p.ldo2 = ldo; p.nlse = nlse;
-  if (o && !al(o, ldo * 2, 4)) return RDST_ENOTSUP;   // (delta reads the head's piece of the output row with dword loads)
+  if (o && !rdst_aligned(4, {o}, {ldo * 2})) return RDST_ENOTSUP;   // (delta reads the head's piece of the output row with dword loads)
   if ((o == nullptr) != (nlse == nullptr)) return RDST_ENOTSUP;
   *nslab = (int)nwin;
   const int d = g.C / 6;
   const int a = d == 10 ? 8 : d == 15 ? 4 : 16;
-  if (!(al(qkv, ld * 2, a) && al(dout, ldd * 2, a) && al(dqkv, ldq * 2, a))) return RDST_ENOTSUP;
+  if (!rdst_aligned(a, {qkv, dout, dqkv}, {ld * 2, ldd * 2, ldq * 2})) return RDST_ENOTSUP;
   if (d == 10) return launch_bwd16<10>(p, st);
   if (d == 15) return launch_bwd16<15>(p, st);
   if (d == 20) return launch_bwd16<20>(p, st);

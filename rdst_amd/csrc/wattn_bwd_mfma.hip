@@ -530,15 +530,6 @@ __global__ void __launch_bounds__(64 * NWAVES) wattn_bwd_mfma_kernel(const WbArg
   }
 }
 
-bool mfma_disabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = rdst_dbg_getenv("RDST_DISABLE_MFMA");
-    v = (e && e[0] == '1') ? 1 : 0;
-  }
-  return v == 1;
-}
-
 template <typename T>
 int launch_bwd(const T* qkv, int64_t ld, const float* table, const T* dout, int64_t ldd, T* dqkv, int64_t ldq,
                float* slab, int slab_rows, const WinGeom& g, float scale, int* nslab, bool split, hipStream_t st) {
@@ -549,20 +540,14 @@ int launch_bwd(const T* qkv, int64_t ld, const float* table, const T* dout, int6
   p.g = g; p.scale = scale; p.d = d;
   { const char* e = rdst_dbg_getenv("RDST_K2_DEBUG"); p.dbg = e ? atoi(e) : 0; }
   const int sec = g.C * (int)sizeof(T);
-  int gran = 0;
-  for (int gs = 16; gs >= 4; gs >>= 1) {
-    const auto ok = [&](const void* q, int64_t l) { return ((uintptr_t)q % gs) == 0 && (l * (int64_t)sizeof(T)) % gs == 0; };
-    if (sec % gs == 0 && ok(qkv, ld) && ok(dout, ldd) && ok(dqkv, ldq)) { gran = gs; break; }
-  }
+  constexpr int64_t TB = sizeof(T);
+  const int gran = wattn_gran(sec, {qkv, dout, dqkv}, {ld * TB, ldd * TB, ldq * TB});
   if (!gran) return RDST_ENOTSUP;
   const int ldt = wb_ldt<T>(g.C);
   p.ldt = ldt;
   const size_t smem = (size_t)4 * 64 * ldt + (size_t)2 * HEADS * 15 * TS * 4 + (size_t)HEADS * 64 * 16;
   if (smem > 160 * 1024) return RDST_ENOTSUP;
-  const int64_t nwin = (int64_t)g.B * g.nWh * g.nWw;
-  int64_t grid = 256;
-  if (grid > nwin) grid = nwin;
-  if (grid > slab_rows) grid = slab_rows;
+  const int64_t grid = k2_groups((int64_t)g.B * g.nWh * g.nWw, slab_rows);
   *nslab = (int)grid;
   const int per_row = 3 * sec / gran;
   const int iters = (per_row + 63) / 64;
@@ -600,38 +585,9 @@ int launch_bwd(const T* qkv, int64_t ld, const float* table, const T* dout, int6
 int wattn_bwd_mfma(const void* qkv, int64_t ld, const float* table, const void* dout, int64_t ldd, void* dqkv,
                    int64_t ldq, float* slab, int slab_rows, const WinGeom& g, float scale, int dtype, bool split, int* nslab,
                    hipStream_t st) {
-  if (mfma_disabled()) return RDST_ENOTSUP;
-  if (dtype == RDST_F32) {
-    const int rc = wattn16_bwd_f32((const float*)qkv, ld, table, (const float*)dout, ldd, (float*)dqkv, ldq, slab, slab_rows, g,
-                                   scale, nslab, st);   // 16x16 windows
-    if (rc != RDST_ENOTSUP) return rc;
+  if (dtype == RDST_F32)
     return launch_bwd<float>((const float*)qkv, ld, table, (const float*)dout, ldd, (float*)dqkv, ldq, slab, slab_rows, g,
                              scale, nslab, split, st);
-  }
-#ifndef RDST_K2_DMA
-#define RDST_K2_DMA 6   // bit mask over the head dims 10 / 15 / 20 (1 / 2 / 4): which widths take the round-4 re-cut (wattn_bwd_pair.hip:
-                        // LDS-DMA ring of section sets, loader / storer waves, passes T / N without the P / dS images).  It hides the row
-                        // traffic but is VALU-bound by its recomputed key-tile pass.  Same box, cold, "K2 + table reduce" per call at
-                        // C = 60 / 90 / 120: 77.6-80.7 / 78.9 / 78.8 us against 76.0 / 80.5 / 82.5 for the kernel below; inside the step
-                        // (rocprofv3, profiles/r04f_*, before the loaders' cheaper issue code) 65.7 / 69.9 / 69.1 against 64.6 / 70.0 / 72.7:
-                        // C = 90 and C = 120 take it, C = 60 (where the old kernel's arithmetic is the cheaper one) does not
-#endif
-  if (g.heads == 6 && g.C % 6 == 0) {
-    const int d6 = g.C / 6;
-    const int bit = d6 == 10 ? 1 : d6 == 15 ? 2 : d6 == 20 ? 4 : 0;
-    if (RDST_K2_DMA & bit) {
-      const int rc = wattn_bwd_pair(qkv, ld, table, dout, ldd, dqkv, ldq, slab, slab_rows, g, scale, nslab, st);
-      if (rc != RDST_ENOTSUP) return rc;
-    }
-  }
-  {  // the compile-time-specialised kernel (6 heads of dim 10/15/20) where it applies
-    const int rc = wattn_bwd_mfma_hd(qkv, ld, table, dout, ldd, dqkv, ldq, slab, slab_rows, g, scale, nslab, st);
-    if (rc != RDST_ENOTSUP) return rc;
-  }
-  {  // 16x16 windows
-    const int rc = wattn16_bwd_mfma(qkv, ld, table, dout, ldd, dqkv, ldq, slab, slab_rows, g, scale, nslab, st);
-    if (rc != RDST_ENOTSUP) return rc;
-  }
   return launch_bwd<bf16>((const bf16*)qkv, ld, table, (const bf16*)dout, ldd, (bf16*)dqkv, ldq, slab, slab_rows, g, scale,
                           nslab, false, st);
 }

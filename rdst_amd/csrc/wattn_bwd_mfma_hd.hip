@@ -572,51 +572,15 @@ int launch_bw(const BwArgs& p, int slab_rows, int* nslab, hipStream_t st) {
   using CF = HdB<D, HEADS>;
   auto kern = wattn_bwd_hd_kernel<D, HEADS, GRAN>;
   constexpr int NT2 = 128 * HEADS, NG = HEADS_ALL / HEADS;
-  const int64_t nwin = (int64_t)p.g.B * p.g.nWh * p.g.nWw;
-  int64_t G = 256;      // window groups: NG workgroups each, 256 x NG workgroups = 12 waves per CU
-  if (G > nwin) G = nwin;
-  if (G > slab_rows) G = slab_rows;
+  const int64_t G = k2_groups((int64_t)p.g.B * p.g.nWh * p.g.nWw, slab_rows);   // NG workgroups each, 256 x NG workgroups = 12 waves per CU
   *nslab = (int)G;
   BwArgs pg = p;
   pg.G = (int)G;
   const int64_t grid = G * NG;
-  static int want_stamps = -1;
-  if (want_stamps < 0) {
-    const char* e = rdst_dbg_getenv("RDST_K2_STAMPS");
-    want_stamps = e ? atoi(e) : 0;
-  }
-  if (want_stamps > 0) {  // debug: in-kernel phase stamps of every workgroup, summarised on stderr
-    BwArgs q = pg;
-    const size_t n = (size_t)grid * 16;
-    (void)hipMalloc((void**)&q.stamps, n * 8);
-    (void)hipMemsetAsync(q.stamps, 0, n * 8, st);
-    const int rc = rdst_launch(kern, dim3((unsigned)grid), dim3(NT2), CF::SMEM, st, "wattn_bwd_hd", q);
-    (void)hipStreamSynchronize(st);
-    unsigned long long* hst = (unsigned long long*)malloc(n * 8);
-    (void)hipMemcpy(hst, q.stamps, n * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(q.stamps);
-    if (--want_stamps == 0) {
-      double sum[16] = {0};
-      int cnt[16] = {0};
-      for (int64_t w = 0; w < grid; ++w)
-        for (int k = 1; k < 16; ++k) {
-          if (!hst[w * 16 + k]) continue;
-          sum[k] += (double)(hst[w * 16 + k] - hst[w * 16 + k - 1]);
-          cnt[k]++;
-        }
-      fprintf(stderr, "[K2 stamps D=%d grid=%lld] mean ticks between consecutive stamps\n", D, (long long)grid);
-      for (int k = 1; k < 16; ++k)
-        if (cnt[k]) fprintf(stderr, "  %2d: %9.0f\n", k, sum[k] / cnt[k]);
-    }
-    free(hst);
-    return rc;
-  }
-  return rdst_launch(kern, dim3((unsigned)grid), dim3(NT2), CF::SMEM, st, "wattn_bwd_hd", pg);
-}
-
-bool aligned_to(const void* a, const void* b, const void* cc, int64_t la, int64_t lb, int64_t lc, int gsz) {
-  return (uintptr_t)a % gsz == 0 && (uintptr_t)b % gsz == 0 && (uintptr_t)cc % gsz == 0 && la % gsz == 0 && lb % gsz == 0 &&
-         lc % gsz == 0;
+  pg.stamps = rdst_stamps_begin("RDST_K2_STAMPS", grid, 16, st);   // (debug: in-kernel stamps of every workgroup)
+  const int rc = rdst_launch(kern, dim3((unsigned)grid), dim3(NT2), CF::SMEM, st, "wattn_bwd_hd", pg);
+  rdst_stamps_end(pg.stamps, grid, 16, RDST_STAMPS_TICKS, st, "K2 D=%d", D);
+  return rc;
 }
 
 }  // namespace
@@ -626,22 +590,16 @@ bool aligned_to(const void* a, const void* b, const void* cc, int64_t la, int64_
 int wattn_bwd_mfma_hd(const void* qkv, int64_t ld, const float* table, const void* dout, int64_t ldd, void* dqkv,
                       int64_t ldq, float* slab, int slab_rows, const WinGeom& g, float scale, int* nslab, hipStream_t st) {
   if (g.ws != 8 || g.heads != 6 || g.mask || !(scale > 0.f) || g.C % 6 || slab_rows < 1) return RDST_ENOTSUP;
-  static int v1 = -1;
-  if (v1 < 0) {
-    const char* e = rdst_dbg_getenv("RDST_K2_V1");
-    v1 = (e && e[0] == '1') ? 1 : 0;
-  }
-  if (v1) return RDST_ENOTSUP;
   BwArgs p{};
   p.qkv = (const bf16*)qkv; p.ld = ld; p.table = table; p.dout = (const bf16*)dout; p.ldd = ldd; p.dqkv = (bf16*)dqkv;
   p.ldq = ldq; p.slab = slab; p.g = g; p.scale = scale;
   const int d = g.C / 6;
-  const int64_t a = ld * 2, b = ldd * 2, cc = ldq * 2;
+  const auto aligned = [&](int gran) { return rdst_aligned(gran, {qkv, dout, dqkv}, {ld * 2, ldd * 2, ldq * 2}); };
 #ifndef K2_NH
 #define K2_NH 6    // heads per workgroup: 6 = one 12-wave workgroup per window (rounds 1-3; now the fallback for strided rows); 2 = (window, head pair) items with register-staged rows, three workgroups per CU (measured round 4: no faster, see wattn_bwd_pair.hip)
 #endif
-  if (d == 10 && aligned_to(qkv, dout, dqkv, a, b, cc, 8)) return launch_bw<10, K2_NH, 8>(p, slab_rows, nslab, st);
-  if (d == 15 && aligned_to(qkv, dout, dqkv, a, b, cc, 4)) return launch_bw<15, K2_NH, 12>(p, slab_rows, nslab, st);
-  if (d == 20 && aligned_to(qkv, dout, dqkv, a, b, cc, 16)) return launch_bw<20, K2_NH, 16>(p, slab_rows, nslab, st);
+  if (d == 10 && aligned(8)) return launch_bw<10, K2_NH, 8>(p, slab_rows, nslab, st);
+  if (d == 15 && aligned(4)) return launch_bw<15, K2_NH, 12>(p, slab_rows, nslab, st);
+  if (d == 20 && aligned(16)) return launch_bw<20, K2_NH, 16>(p, slab_rows, nslab, st);
   return RDST_ENOTSUP;
 }

@@ -657,10 +657,7 @@ template <int D>
 int launch_pair(const PArgs& p0, int slab_rows, int* nslab, hipStream_t st) {
   using CF = PC<D>;
   auto kern = wattn_bwd_pair_kernel<D>;
-  const int64_t nwin = (int64_t)p0.g.B * p0.g.nWh * p0.g.nWw;
-  int64_t G = 256;      // window groups x 3 pairs = 768 workgroups = three per CU
-  if (G > nwin) G = nwin;
-  if (G > slab_rows) G = slab_rows;
+  const int64_t G = k2_groups((int64_t)p0.g.B * p0.g.nWh * p0.g.nWw, slab_rows);   // x 3 pairs = 768 workgroups = three per CU
   *nslab = (int)G;
   PArgs p = p0;
   p.G = (int)G;
@@ -678,15 +675,8 @@ int wattn_bwd_pair(const void* qkv, int64_t ld, const float* table, const void* 
   if (ld != 3 * g.C || ldq != 3 * g.C || ldd != g.C) return RDST_ENOTSUP;
   const int64_t ntok = (int64_t)g.B * g.H * g.W;
   if (ntok * 3 * g.C * 2 >= (1ll << 31)) return RDST_ENOTSUP;
-  static int off = -1;
-  if (off < 0) {
-    const char* e = rdst_dbg_getenv("RDST_K2_PAIR");
-    off = (e && e[0] == '0') ? 1 : 0;
-  }
-  if (off) return RDST_ENOTSUP;
   const int d = g.C / 6;
-  const int gran = d == 10 ? 8 : d == 15 ? 4 : 16;
-  if ((uintptr_t)qkv % gran || (uintptr_t)dout % gran || (uintptr_t)dqkv % gran) return RDST_ENOTSUP;
+  if (!rdst_aligned(d == 10 ? 8 : d == 15 ? 4 : 16, {qkv, dout, dqkv}, {})) return RDST_ENOTSUP;
   PArgs p{};
   p.qkv = (const bf16*)qkv; p.dout = (const bf16*)dout; p.dqkv = (bf16*)dqkv; p.table = table; p.slab = slab;
   p.ld = ld; p.ldd = ldd; p.ldq = ldq; p.g = g; p.scale = scale;

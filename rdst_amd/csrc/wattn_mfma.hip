@@ -354,21 +354,6 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? (sizeof(T) == 2 ? 3 : 2) : 
   }
 }
 
-bool mfma_disabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = rdst_dbg_getenv("RDST_DISABLE_MFMA");
-    v = (e && e[0] == '1') ? 1 : 0;
-  }
-  return v == 1;
-}
-
-int pick_gran(uintptr_t a, uintptr_t b, int64_t lda_bytes, int64_t ldb_bytes, int sec_bytes) {
-  for (int gsz = 16; gsz >= 4; gsz >>= 1)
-    if (a % gsz == 0 && b % gsz == 0 && lda_bytes % gsz == 0 && ldb_bytes % gsz == 0 && sec_bytes % gsz == 0) return gsz;
-  return 0;
-}
-
 template <typename T>
 int launch_fwd(const T* qkv, int64_t ld, const float* table, T* out, int64_t ldo, const WinGeom& g, float scale,
                bool split, hipStream_t st) {
@@ -378,7 +363,7 @@ int launch_fwd(const T* qkv, int64_t ld, const float* table, T* out, int64_t ldo
   p.qkv = qkv; p.ld = ld; p.table = table; p.out = out; p.ldo = ldo; p.g = g; p.scale = scale; p.d = d;
   { const char* e = rdst_dbg_getenv("RDST_K1_DEBUG"); p.dbg = e ? atoi(e) : 0; }
   const int sec = g.C * (int)sizeof(T);
-  p.gran = pick_gran((uintptr_t)qkv, (uintptr_t)out, ld * (int64_t)sizeof(T), ldo * (int64_t)sizeof(T), sec);
+  p.gran = wattn_gran(sec, {qkv, out}, {ld * (int64_t)sizeof(T), ldo * (int64_t)sizeof(T)});
   if (!p.gran) return RDST_ENOTSUP;
   // section row stride: whole k-steps, 16-B aligned, odd number of 16-B slots
   int ldt = ((sec + 31) / 32) * 32;
@@ -421,19 +406,6 @@ int launch_fwd(const T* qkv, int64_t ld, const float* table, T* out, int64_t ldo
 
 int wattn_fwd_mfma(const void* qkv, int64_t ld, const float* table, void* out, int64_t ldo, const WinGeom& g,
                    float scale, int dtype, bool split, hipStream_t st) {
-  if (mfma_disabled()) return RDST_ENOTSUP;
-  if (dtype == RDST_F32) {
-    const int rc = wattn16_fwd_f32((const float*)qkv, ld, table, (float*)out, ldo, g, scale, st);   // 16x16 windows
-    if (rc != RDST_ENOTSUP) return rc;
-    return launch_fwd<float>((const float*)qkv, ld, table, (float*)out, ldo, g, scale, split, st);
-  }
-  {  // the compile-time-specialised kernel (6 heads of dim 10/15/20) where it applies
-    const int rc = wattn_fwd_mfma_hd(qkv, ld, table, out, ldo, g, scale, st);
-    if (rc != RDST_ENOTSUP) return rc;
-  }
-  {  // 16x16 windows
-    const int rc = wattn16_fwd_mfma(qkv, ld, table, out, ldo, g, scale, st);
-    if (rc != RDST_ENOTSUP) return rc;
-  }
+  if (dtype == RDST_F32) return launch_fwd<float>((const float*)qkv, ld, table, (float*)out, ldo, g, scale, split, st);
   return launch_fwd<bf16>((const bf16*)qkv, ld, table, (bf16*)out, ldo, g, scale, false, st);
 }

@@ -428,48 +428,11 @@ int launch_hd(const HdArgs& p, hipStream_t st) {
   }
   int64_t grid = 256 * (int64_t)wg_per_cu;
   if (grid > nwin) grid = nwin;
-  static int want_stamps = -1;
-  if (want_stamps < 0) {
-    const char* e = rdst_dbg_getenv("RDST_K1_STAMPS");
-    want_stamps = e ? atoi(e) : 0;
-  }
-  if (want_stamps > 0) {  // debug: in-kernel phase stamps of every workgroup, summarised on stderr
-    HdArgs q = p;
-    const size_t n = (size_t)grid * 16;
-    (void)hipMalloc((void**)&q.stamps, n * 8);
-    (void)hipMemsetAsync(q.stamps, 0, n * 8, st);
-    const int rc = rdst_launch(kern, dim3((unsigned)grid), dim3(256), CF::SMEM, st, "wattn_fwd_hd", q);
-    (void)hipStreamSynchronize(st);
-    unsigned long long* hst = (unsigned long long*)malloc(n * 8);
-    (void)hipMemcpy(hst, q.stamps, n * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(q.stamps);
-    unsigned long long t0 = ~0ull;
-    for (int64_t w = 0; w < grid; ++w) if (hst[w * 16] && hst[w * 16] < t0) t0 = hst[w * 16];
-    if (--want_stamps == 0) {  // print for the last requested launch only
-      double sum[16] = {0}, mx[16] = {0}, mn[16];
-      int cnt[16] = {0};
-      for (int k = 0; k < 16; ++k) mn[k] = 1e30;
-      for (int64_t w = 0; w < grid; ++w)
-        for (int k = 0; k < 16; ++k) {
-          const unsigned long long t = hst[w * 16 + k];
-          if (!t) continue;
-          const double d = (double)(t - hst[w * 16]);  // relative to the workgroup's own start (clocks differ per XCD)
-          sum[k] += d; cnt[k]++;
-          if (d > mx[k]) mx[k] = d;
-          if (d < mn[k]) mn[k] = d;
-        }
-      fprintf(stderr, "[K1 stamps D=%d grid=%lld] ticks since the workgroup's own start (k: n mean min max)\n", D, (long long)grid);
-      for (int k = 0; k < 16; ++k)
-        if (cnt[k]) fprintf(stderr, "  %2d: %5d %9.0f %9.0f %9.0f\n", k, cnt[k], sum[k] / cnt[k], mn[k], mx[k]);
-    }
-    free(hst);
-    return rc;
-  }
-  return rdst_launch(kern, dim3((unsigned)grid), dim3(256), CF::SMEM, st, "wattn_fwd_hd", p);
-}
-
-bool aligned_to(const void* a, const void* b, int64_t lda_bytes, int64_t ldb_bytes, int gsz) {
-  return (uintptr_t)a % gsz == 0 && (uintptr_t)b % gsz == 0 && lda_bytes % gsz == 0 && ldb_bytes % gsz == 0;
+  HdArgs q = p;   // (debug: in-kernel stamps of every workgroup, relative to its own start: the clocks differ per XCD)
+  q.stamps = rdst_stamps_begin("RDST_K1_STAMPS", grid, 16, st);
+  const int rc = rdst_launch(kern, dim3((unsigned)grid), dim3(256), CF::SMEM, st, "wattn_fwd_hd", q);
+  rdst_stamps_end(q.stamps, grid, 16, RDST_STAMPS_TICKS, st, "K1 D=%d", D);
+  return rc;
 }
 
 }  // namespace
@@ -478,12 +441,6 @@ bool aligned_to(const void* a, const void* b, int64_t lda_bytes, int64_t ldb_byt
 int wattn_fwd_mfma_hd(const void* qkv, int64_t ld, const float* table, void* out, int64_t ldo, const WinGeom& g,
                       float scale, hipStream_t st) {
   if (g.ws != 8 || g.heads != 6 || g.mask || !(scale > 0.f) || g.C % 6) return RDST_ENOTSUP;
-  static int v1 = -1;
-  if (v1 < 0) {
-    const char* e = rdst_dbg_getenv("RDST_K1_V1");
-    v1 = (e && e[0] == '1') ? 1 : 0;
-  }
-  if (v1) return RDST_ENOTSUP;
   HdArgs p{};
   p.qkv = (const bf16*)qkv; p.ld = ld; p.table = table; p.out = (bf16*)out; p.ldo = ldo; p.g = g; p.scale = scale;
   { const char* e = rdst_dbg_getenv("RDST_K1_DEBUG"); p.dbg = e ? atoi(e) : 0; }
@@ -494,8 +451,9 @@ int wattn_fwd_mfma_hd(const void* qkv, int64_t ld, const float* table, void* out
     const char* e = rdst_dbg_getenv("RDST_K1_MINB");
     minb = e ? atoi(e) : 0;
   }
-  if (d == 10 && aligned_to(qkv, out, lb, lob, 8)) return minb == 4 ? launch_hd<10, 6, 8, 1, 4>(p, st) : launch_hd<10, 6, 8, 1, 3>(p, st);
-  if (d == 15 && aligned_to(qkv, out, lb, lob, 4)) return launch_hd<15, 6, 12, 1, 3>(p, st);
-  if (d == 20 && aligned_to(qkv, out, lb, lob, 16)) return launch_hd<20, 6, 16, 1, 2>(p, st);
+  const auto aligned = [&](int gran) { return rdst_aligned(gran, {qkv, out}, {lb, lob}); };
+  if (d == 10 && aligned(8)) return minb == 4 ? launch_hd<10, 6, 8, 1, 4>(p, st) : launch_hd<10, 6, 8, 1, 3>(p, st);
+  if (d == 15 && aligned(4)) return launch_hd<15, 6, 12, 1, 3>(p, st);
+  if (d == 20 && aligned(16)) return launch_hd<20, 6, 16, 1, 2>(p, st);
   return RDST_ENOTSUP;
 }

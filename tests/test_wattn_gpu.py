@@ -54,7 +54,15 @@ def test_wattn_fwd_bwd_fp32(B, H, W, C, heads, ws, shift):
     assert rel <= 1e-5, rel
 
 
-@pytest.mark.parametrize("B,H,W,C,heads,ws,shift", CASES[:5])
+# the rows of the bf16 route tables (csrc/wattn_api.hip) that CASES[:5] and the tests below do not reach: two windows each
+BF16_ROUTE_CASES = [
+    (1, 8, 16, 48, 6, 8, 4),      # head dim 8: the generic matrix-core kernels, forward and backward
+    (1, 8, 16, 60, 3, 8, 4),      # 3 heads: generic matrix-core forward, scalar backward
+    (1, 8, 16, 48, 6, 4, 2),      # window 4: the scalar kernels both ways
+]
+
+
+@pytest.mark.parametrize("B,H,W,C,heads,ws,shift", CASES[:5] + BF16_ROUTE_CASES)
 def test_wattn_fwd_bwd_bf16(B, H, W, C, heads, ws, shift):
     from rdst_amd import ops
     dev = torch.device("cuda:0")

@@ -39,7 +39,7 @@ KERNELS = {
     "lin_mfma_kernel": ("lin_mfma_kernel", ["linear_mfma.hip"]),
     "mlp_fwd_kernel": ("mlp_fwd_kernel", ["mlp_mfma.hip"]),
     "mlp_bwd_kernel": ("mlp_bwd_kernel", ["mlp_mfma.hip"]),
-    "lnlin_bwd_kernel": ("lnlin_bwd_kernel", ["mlp_mfma.hip"]),
+    "lnlin_bwd_kernel": ("lnlin_bwd_kernel", ["lnlin_mfma.hip"]),
     "lnlin3_bwd_kernel": ("lnlin3_bwd_kernel", ["lnlin3_mfma.hip"]),
     "lin3_kernel": ("lin3_kernel", ["lin3_mfma.hip"]),
     "mlp3_fwd_kernel": ("mlp3_fwd_kernel", ["mlp3_mfma.hip"]),

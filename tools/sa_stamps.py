@@ -1,4 +1,5 @@
-"""Per-phase cycle stamps of K8 (diagnostic library rdst_amd/lib_sa_stamps.so built with -DSA_STAMPS): one launch per width.
+"""Per-phase cycle stamps of K8: one launch per width on the diagnostic library rdst_amd/lib_sa_stamps.so
+(bash tools/abl_build.sh rdst_amd/csrc/swinattn_fwd.hip sa_stamps -DSA_STAMPS -DRDST_DEBUG).
 usage: RDST_HIP_LIB=$PWD/rdst_amd/lib_sa_stamps.so SA_STAMPS_N=1 python tools/sa_stamps.py C"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
