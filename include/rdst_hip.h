@@ -631,6 +631,34 @@ int rdst_adam_step_dev_ema(float* param, const float* grad, float* exp_avg, floa
  * or misaligned (16 B) pointer, n < 0, or ranges that overlap. */
 int rdst_swap_f32(float* a, float* b, int64_t n, void* stream);
 
+/* ---- SSIM training loss: value and gradient in one kernel (rdst_amd/loss/ssim.py) -----------------------------------------
+ * loss = 1 - mean_n ssim[n] of a prediction against a target, both fp32 NCHW and contiguous, and d loss / d pred.
+ * Definition (the tests' float64 reference computes exactly this).  Taps w_0 .. w_{win-1} with sum 1 (the 2-D weight is
+ * w_k w_l), valid windows only (Ho = H - win + 1, Wo = W - win + 1), F(.) the weighted window sum at a valid position,
+ * X = target, Y = pred:
+ *   ux = F(X)  uy = F(Y)  uxx = F(X^2)  uyy = F(Y^2)  uxy = F(XY)
+ *   vx = cn (uxx - ux^2)  vy = cn (uyy - uy^2)  vxy = cn (uxy - ux uy)                         cn = cov_norm
+ *   A1 = 2 ux uy + C1   A2 = 2 vxy + C2   B1 = ux^2 + uy^2 + C1   B2 = vx + vy + C2
+ *   C1 = (0.01 data_range)^2   C2 = (0.03 data_range)^2
+ *   S = A1 A2 / (B1 B2);   ssim[n] = mean over channels and valid positions of S;   loss = 1 - mean_n ssim[n]
+ * With uniform taps 1 / win and cov_norm = win^2 / (win^2 - 1) ssim[n] is rdst_sr_scores' at margin 0.  The gradient:
+ *   a = 2 ux A2 / (B1 B2) - 2 uy S / B1 - 2 cn ux A1 / (B1 B2) + 2 cn uy S / B2,   b = -cn S / B2,   c = 2 cn A1 / (B1 B2)
+ *   grad[p] = -(sum_q w(p - q) a_q + 2 Y[p] sum_q w(p - q) b_q + X[p] sum_q w(p - q) c_q) / (N C Ho Wo)
+ * over the valid positions q whose window holds pixel p.  All window arithmetic is fp64 (products of two fp32 values are
+ * exact there); every gradient element is rounded to fp32 once and written once.
+ *   taps       HOST array of win doubles, or NULL for the uniform window; copied into the kernel's arguments by value
+ *   ssim       device, N doubles;   loss   device, 1 float = (float)(1 - mean ssim), may be NULL
+ *   grad       device, N*C*H*W floats, d loss / d pred for an upstream gradient of 1; NULL = value only
+ *   workspace  device memory of at least rdst_ssim_loss_workspace(...) bytes (0 for bad arguments): one fp64 sum per
+ *              workgroup, summed per image in a fixed order by a second kernel — bit-identical run to run, no atomics.
+ * RDST_EINVAL before any launch: a non-positive size, win even or outside [3, 15], H or W below win, more than 2^31
+ * pixels, a null target / pred / ssim / workspace, a short workspace, a non-finite tap or taps that do not sum to 1 within
+ * 1e-9, cov_norm <= 0, data_range <= 0. */
+size_t rdst_ssim_loss_workspace(int N, int C, int H, int W, int win);
+int rdst_ssim_loss(const float* target, const float* pred, int N, int C, int H, int W, int win, const double* taps,
+                   double cov_norm, double data_range, double* ssim, float* loss, float* grad, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

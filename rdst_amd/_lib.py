@@ -113,6 +113,9 @@ SIGNATURES = {
     "rdst_adam_step_ema": (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _l, C.c_double, _i, _p]),
     "rdst_adam_step_dev_ema": (_i, [_p, _p, _p, _p, _p, _l, LrSchedule, _f, _f, _f, _f, C.c_double, _i, _p, _p]),
     "rdst_swap_f32": (_i, [_p, _p, _l, _p]),
+    # the SSIM training loss (rdst_amd.loss.ssim_loss): additive entry points, the ABI version stays
+    "rdst_ssim_loss_workspace": (_z, [_i, _i, _i, _i, _i]),
+    "rdst_ssim_loss": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, C.c_double, C.c_double, _p, _p, _p, _p, _z, _p]),
 }
 
 ABI_VERSION = 11             # must equal rdst_abi_version() of the loaded library (argument lists change between versions)

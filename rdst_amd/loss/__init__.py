@@ -1,2 +1,3 @@
 from .seg_unet import SegUNet_F  # noqa: F401
 from .sr_loss import LazyScalars, RecLoss, SRLoss  # noqa: F401
+from .ssim import SSIMLoss, ssim_loss, window_taps  # noqa: F401

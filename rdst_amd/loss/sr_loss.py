@@ -1,6 +1,8 @@
 """The weighted training loss of the reference trainer (loss/sr_loss.py:11-51, loss/basic_loss.py:14-95) for the loss
 components that sit on this repository's path: 'L1' / 'L2' / 'MSE' (``RecLoss``, sr_loss.py:60-72) and 'UNet-F'
-(``SegUNet_F``, loss/seg_unet.py).  VGG / GAN components are outside SURVEY.md section 8 and raise.
+(``SegUNet_F``, loss/seg_unet.py).  VGG / GAN components are outside SURVEY.md section 8 and raise.  'SSIM' (``SSIMLoss``,
+ssim.py) is this repository's own addition: ``1 - SSIM`` from one HIP kernel, e.g. ``{'L1': 0.16, 'SSIM': 0.84}``; optional
+``paras.ssim_window`` ('uniform' / 'gaussian'), ``ssim_win_size``, ``ssim_sigma`` and ``ssim_data_range`` configure it.
 
     loss, repo = SRLoss(paras)(pred, gt)       # sum_n scalars[state][n] * component_n(pred, gt)
 
@@ -19,6 +21,7 @@ import torch
 import torch.nn.functional as F
 
 from .seg_unet import SegUNet_F
+from .ssim import SSIMLoss
 
 
 class LazyScalars(dict):
@@ -81,10 +84,14 @@ class SRLoss(object):
                 self.use_seg_loss_flag = True
                 f = SegUNet_F(paras.unet_loss_layers, paras.unet_loss_mode, unet_path=getattr(paras, "unet_path", None),
                               allow_random_init=bool(getattr(paras, "unet_allow_random", False))).to(self.device)
+            elif l in ["SSIM"]:
+                f = SSIMLoss(window=getattr(paras, "ssim_window", "uniform"), win_size=getattr(paras, "ssim_win_size", None),
+                             sigma=getattr(paras, "ssim_sigma", 1.5), data_range=getattr(paras, "ssim_data_range", 1.0))
             else:
                 raise NotImplementedError(
                     "rdst_amd.loss.SRLoss: loss component {!r} is outside this repository's scope (SURVEY.md section 8: "
-                    "L1 / L2 / MSE and UNet-F are on the path; VGG and GAN losses are not)".format(l))
+                    "L1 / L2 / MSE and UNet-F are on the path, SSIM is this repository's own; VGG and GAN losses are "
+                    "not)".format(l))
             self.loss_components += f.loss_names
             self.loss_functions[l] = f
 
