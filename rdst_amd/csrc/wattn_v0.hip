@@ -88,7 +88,10 @@ wattn_fwd_v0(const T* __restrict__ qkv, int64_t ld, const float* __restrict__ ta
   }
 }
 
-// smem carve (floats): Qs Ks Vs dOs [N*D each] lse[N] delta[N] tab[T] dtab[T] | ints trow[N] reg[N]
+// smem carve (floats): Qs Ks Vs dOs [N*D each] rmax[N] rinv[N] delta[N] tab[T] dtab[T] | ints trow[N] reg[N]
+// P is formed as in the forward, expf(s - max) * (1 / sum), from the row maximum and the reciprocal of the row sum: a stored
+// log-sum-exp max + logf(sum) is rounded at the magnitude of the maximum and P = expf(s - lse) inherits that (2^-18 relative
+// for a row whose every logit is near -100), so the softmax would not be shift-invariant to fp32 accuracy
 template <typename T, int D>
 __global__ void __launch_bounds__(256)
 wattn_bwd_v0(const T* __restrict__ qkv, int64_t ld, const float* __restrict__ table,
@@ -100,8 +103,9 @@ wattn_bwd_v0(const T* __restrict__ qkv, int64_t ld, const float* __restrict__ ta
   float* Ks = Qs + N * D;
   float* Vs = Ks + N * D;
   float* dOs = Vs + N * D;
-  float* lse = dOs + N * D;
-  float* delta = lse + N;
+  float* rmax = dOs + N * D;
+  float* rinv = rmax + N;
+  float* delta = rinv + N;
   float* tab = delta + N;
   float* dtab = tab + TT;
   int* trow = reinterpret_cast<int*>(dtab + TT);
@@ -139,7 +143,7 @@ wattn_bwd_v0(const T* __restrict__ qkv, int64_t ld, const float* __restrict__ ta
   const bool drop = g.pdrop > 0.f;
   const unsigned long long seed = drop ? *g.seed : 0ull;
   const float rkeep = drop ? 1.0f / (1.0f - g.pdrop) : 1.0f;
-  // ---- pass A: one lane per query row: lse, delta, dQ, d(table) -------------------------------
+  // ---- pass A: one lane per query row: row maximum and 1 / sum, delta, dQ, d(table) -----------
   for (int i = tid; i < N; i += bd) {
     float q[D], dO[D];
 #pragma unroll
@@ -177,8 +181,9 @@ wattn_bwd_v0(const T* __restrict__ qkv, int64_t ld, const float* __restrict__ ta
 #pragma unroll
     for (int e = 0; e < D; ++e) dl = fmaf(dO[e], acc[e], dl);
     dl /= l;                       // delta_i = dO_i . O_i = sum_j P_ij dP_ij
-    const float ls = m + logf(l);  // log-sum-exp of row i
-    lse[i] = ls;
+    const float inv = 1.0f / l;
+    rmax[i] = m;
+    rinv[i] = inv;
     delta[i] = dl;
     float dq[D];
 #pragma unroll
@@ -194,7 +199,7 @@ wattn_bwd_v0(const T* __restrict__ qkv, int64_t ld, const float* __restrict__ ta
         const int ti = base - yj * tw - xj;
         s += tab[ti];
         if (mrow) s += mrow[j]; else if (g.shift > 0 && reg[j] != ri) s += -100.0f;
-        const float p = expf(s - ls);
+        const float p = expf(s - m) * inv;
         if (drop) dp *= wattn_drop_mul(seed, blockIdx.x, i, j, N, g.pdrop, rkeep);
         const float ds = p * (dp - dl);
 #pragma unroll
@@ -224,7 +229,7 @@ wattn_bwd_v0(const T* __restrict__ qkv, int64_t ld, const float* __restrict__ ta
         }
         s += tab[base + yi * tw + xi];
         if (mcol) s += mcol[(int64_t)i * N]; else if (g.shift > 0 && reg[i] != rj) s += -100.0f;
-        const float p = expf(s - lse[i]);
+        const float p = expf(s - rmax[i]) * rinv[i];
         const float mm = drop ? wattn_drop_mul(seed, blockIdx.x, i, j, N, g.pdrop, rkeep) : 1.0f;
         const float ds = p * (mm * dp - delta[i]);
         const float pm = p * mm;
@@ -272,7 +277,7 @@ template <typename T>
 int launch_bwd_d(int D, const T* qkv, int64_t ld, const float* table, const T* dout, int64_t ldd, T* dqkv,
                  int64_t ldq, float* slab, const WinGeom& g, float scale, hipStream_t st) {
   const int N = g.N;
-  const size_t smem = (size_t)(4 * N * D + 2 * N + 2 * g.T) * 4 + (size_t)2 * N * 4;
+  const size_t smem = (size_t)(4 * N * D + 3 * N + 2 * g.T) * 4 + (size_t)2 * N * 4;
   if (smem > 160 * 1024) return rdst_fail(RDST_ENOTSUP, "rdst_wattn_bwd: window %d x head dim %d exceeds LDS", g.ws, D);
   const int bd = N >= 256 ? 256 : ((N + 63) / 64) * 64;
   const dim3 grid((unsigned)((int64_t)g.B * g.nWh * g.nWw * g.heads));
