@@ -7,8 +7,17 @@
 #include <stdarg.h>
 #include <initializer_list>
 #include "../../include/rdst_hip.h"
+#include "workspace.h"
 
 typedef __hip_bfloat16 bf16;
+
+// One workgroup per CU on this part (MI355X: 256 CUs): the unit of every persistent grid cap and of every per-workgroup slab
+// region's row count.  Nothing queries the device; a port to another part changes the grids here and nowhere else.
+constexpr int kCUs = 256;
+// rows of the `small` regions of the Linear and conv backward workspaces (column sums, LayerNorm d(gamma) / d(beta) partials)
+constexpr int kSmallBlocks = 2 * kCUs;
+// floats kept free behind some regions of the backward workspaces: no kernel writes them, the totals have always held them
+constexpr int kWsSlackFloats = 64;
 
 // Ablation switches, in-kernel cycle stamps and environment overrides exist only in a -DRDST_DEBUG build
 // (RDST_BUILD_DEBUG=1 python -m rdst_amd.build; tools/ use it).  In the shipped library RDST_DBGV(x) is the
@@ -159,6 +168,14 @@ static inline int64_t rdst_tile_grid(int64_t ntiles, int64_t cap, int* tiles_per
   const int64_t grid = ntiles < cap ? ntiles : cap;
   *tiles_per_wg = (int)((ntiles + grid - 1) / grid);
   return (ntiles + *tiles_per_wg - 1) / *tiles_per_wg;
+}
+
+// In front of every launch that writes one slab row per workgroup: `grid` rows of `stride` floats fit the workspace region.
+// The caps come from the same region (WsSlab::cap), so this never fires unless a layout and a launcher stop agreeing.
+static inline int rdst_slab_fits(const WsSlab& r, int64_t grid, int64_t stride, const char* what) {
+  if (r.fits(grid, stride)) return 0;
+  return rdst_fail(RDST_EINVAL, "%s: %lld slab rows of %lld floats do not fit the workspace region (%lld x %lld)", what,
+                   (long long)grid, (long long)stride, (long long)r.rows, (long long)r.stride);
 }
 
 // The compute mode of an entry point's dtype, decoded first thing: `dtype` becomes the element type of the rows (RDST_BF16 or

@@ -117,14 +117,11 @@ struct ConvSlabEp {  // wgrad split-K partials, already in nn.Conv2d weight orde
   }
 };
 
-constexpr int kSmallBlocks = 512;
-constexpr int kMaxSplits = 128;
-
 int wgrad_splits(const ConvGeom& g) {
   const int tiles = ((g.Cout + 63) / 64) * ((g.ks * g.ks * g.Cin + 63) / 64);
   int s = 1024 / tiles;
   if (s < 1) s = 1;
-  if (s > kMaxSplits) s = kMaxSplits;
+  if (s > kConvSplits) s = kConvSplits;
   return s;
 }
 
@@ -158,16 +155,10 @@ int bwd_impl(const T* X, int64_t ldx, int in_act, const float* Wc, const T* dY, 
              const T* acc, int64_t ldacc, float* dW, float* dbias, float* wsp, const ConvGeom& g, float s, bool split, hipStream_t st,
              hipStream_t wst) {
   const int64_t wtotal = (int64_t)g.Cout * g.Cin * g.ks * g.ks;
-  // workspace carve: [packed dgrad weights][generic split-K slab][small][MFMA scratch: un-shuffled dY, wgrad slab]
-  void* wpack = wsp;
-  wsp = reinterpret_cast<float*>(reinterpret_cast<char*>(wsp) + conv3x_pack_bytes(g.Cin, g.Cout));   // (room for the hi / lo image: twice the bf16 one)
-  float* w3slab = wsp;
-  wsp = reinterpret_cast<float*>(reinterpret_cast<char*>(wsp) + (g.ks == 3 ? conv3_wgrad_slab_bytes(g.Cin, g.Cout) : 0));
-  float* slab = wsp;
-  float* small = slab + (int64_t)kMaxSplits * wtotal;
-  char* mscr = reinterpret_cast<char*>(small + (int64_t)kSmallBlocks * g.Cout + 64);
+  const ConvBwdWs w = conv_bwd_layout(wsp, g.B, g.H, g.W, g.Cin, g.Cout, g.ks, g.r);
+  void* const wpack = w.wpack;
+  const WsSlab &w3slab = w.w3slab, &c1slab = w.c1slab;
   if constexpr (sizeof(T) == 2) {   // the one-output-channel tail conv: vector kernels, its own slab at the end of the workspace
-    float* c1slab = reinterpret_cast<float*>(mscr + conv_mfma_scratch_bytes(ConvGeom{g.B, g.H, g.W, g.Cin, g.Cout, g.ks, g.pad, 2}));
     if (int rc = conv_c1_bwd_bf16(X, ldx, in_act, Wc, dY, lddy, dX, lddx, acc, ldacc, dW, dbias, c1slab, g, s, st, wst); rc != RDST_ENOTSUP)
       return rc;
     if (!dX && (dW || dbias) && g.r == 1) {   // one input channel (the head conv: no data gradient, the input is the image)
@@ -175,7 +166,6 @@ int bwd_impl(const T* X, int64_t ldx, int in_act, const float* Wc, const T* dY, 
     }
   }
   if constexpr (sizeof(T) == 4) {   // the one-channel convs on fp32 rows (conv_c1x.hip)
-    float* c1slab = reinterpret_cast<float*>(mscr + conv_mfma_scratch_bytes(ConvGeom{g.B, g.H, g.W, g.Cin, g.Cout, g.ks, g.pad, 2}));
     if (int rc = conv_c1x_bwd_f32(X, ldx, in_act, Wc, dY, lddy, dX, lddx, acc, ldacc, dW, dbias, c1slab, g, s, st); rc != RDST_ENOTSUP)
       return rc;
     if (!dX && (dW || dbias) && g.r == 1) {
@@ -212,27 +202,27 @@ int bwd_impl(const T* X, int64_t ldx, int in_act, const float* Wc, const T* dY, 
   // MFMA fast paths want dY as plain (B*H*W, Cout) rows
   int prc = 0;
   int64_t ldp = lddy;
-  const T* dYp = plain_dy<T>(dY, lddy, g, mscr, ldp, st, prc);
+  const T* dYp = plain_dy<T>(dY, lddy, g, w.dYp, ldp, st, prc);
   if (prc) return prc;
-  float* mslab = reinterpret_cast<float*>(mscr + (g.r > 1 ? (size_t)g.pixels() * g.Cout * 4 : 0));
   bool wdone = false;
   if (dW || dbias) {
-    const int rc = conv_wgrad_mfma<T>(X, ldx, in_act, dYp, ldp, dW, dbias, mslab, g, s, split, st);
+    const int rc = conv_wgrad_mfma<T>(X, ldx, in_act, dYp, ldp, dW, dbias, w.mslab, g, s, split, st);
     if (rc == 0) wdone = true;
     else if (rc != RDST_ENOTSUP) return rc;
   }
   if (!wdone && dbias) {
     ConvDyCol<T> f{dY, lddy, g, s};
-    if (int rc = colsum_launch(f, g.pixels(), g.Cout, small, kSmallBlocks, dbias, st, "conv_dbias")) return rc;
+    if (int rc = colsum_launch(f, g.pixels(), g.Cout, w.small, dbias, st, "conv_dbias")) return rc;
   }
   if (!wdone && dW) {
     ConvDyAT<T> la{dY, lddy, g, s};
     ConvAT<T> lb{ConvA<T>{X, ldx, g, in_act}};
-    ConvSlabEp ep{slab, g};
+    ConvSlabEp ep{w.slab.p, g};
     const int splits = wgrad_splits(g);
     const int z = gemm_valu_splits(g.pixels(), splits);
-    int rc = gemm_valu_launch(la, lb, ep, g.Cout, g.ks * g.ks * g.Cin, g.pixels(), splits, st, "conv_wgrad");
-    if (!rc) rc = slab_reduce(slab, dW, z, wtotal, st);
+    int rc = rdst_slab_fits(w.slab, z, wtotal, "conv_wgrad");
+    if (!rc) rc = gemm_valu_launch(la, lb, ep, g.Cout, g.ks * g.ks * g.Cin, g.pixels(), splits, st, "conv_wgrad");
+    if (!rc) rc = slab_reduce(w.slab.p, dW, z, wtotal, st);
     if (rc) return rc;
   }
   if (dX && !dxdone) {
@@ -333,9 +323,7 @@ extern "C" int rdst_conv_fwd(const void* X, int64_t ld_x, int in_act, const floa
 
 extern "C" size_t rdst_conv_bwd_workspace(int B, int H, int W, int Cin, int Cout, int ksize) {
   if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || ksize <= 0) return 0;
-  ConvGeom g{B, H, W, Cin, Cout, ksize, ksize / 2, 2};  // r = 2 reserves room for an un-shuffled dY
-  return conv3x_pack_bytes(Cin, Cout) + (ksize == 3 ? conv3_wgrad_slab_bytes(Cin, Cout) : 0) + sizeof(float) * ((size_t)kMaxSplits * Cout * Cin * ksize * ksize + (size_t)kSmallBlocks * Cout + 64) +
-         conv_mfma_scratch_bytes(g) + sizeof(float) * (Cin == 1 ? conv_in1_slab_floats(Cout) : conv_c1_slab_floats(Cin));
+  return conv_bwd_layout(nullptr, B, H, W, Cin, Cout, ksize, 2).bytes;   // r = 2 reserves room for an un-shuffled dY
 }
 
 extern "C" int rdst_conv_bwd(const void* X, int64_t ld_x, int in_act, const float* Wc, const void* dY, int64_t ld_dy,

@@ -243,12 +243,13 @@ __global__ void __launch_bounds__(256) conv3_wgrad_reduce_kernel(const float* __
 }
 
 template <int CI, int CO, bool UNSHUF>
-int launch_w3(W3Args& p, float s, float* dW, float* dbias, hipStream_t st, const char* what) {
+int launch_w3(W3Args& p, const WsSlab& slab, float s, float* dW, float* dbias, hipStream_t st, const char* what) {
   using CF = W3Cfg<CI, CO, UNSHUF>;
-  Conv3Strips sp;
-  if (!conv3_strip_plan(p.B, p.H, p.W, CF::RPS, 256 / CF::ROLES, sp)) return RDST_ENOTSUP;
+  Conv3Strips sp;   // (a workgroup's row: SLABF / 2 words of bf16 pairs)
+  if (!conv3_strip_plan(p.B, p.H, p.W, CF::RPS, (int)slab.cap(kCUs, CF::SLABF / 2) / CF::ROLES, sp)) return RDST_ENOTSUP;
   p.SH = sp.SH; p.nys = sp.nys; p.nstrips = sp.nstrips; p.npg = sp.npg;
   const int grid = p.npg * CF::ROLES;
+  if (int rc = rdst_slab_fits(slab, grid, CF::SLABF / 2, what)) return rc;
   auto kern = conv3_wgrad_kernel<CI, CO, UNSHUF>;
   if (int rc = rdst_launch(kern, dim3((unsigned)grid), dim3(512), CF::SMEM, st, what, p)) return rc;
   const int tot = CF::ROLES * CF::SLABF / 2;
@@ -258,28 +259,35 @@ int launch_w3(W3Args& p, float s, float* dW, float* dbias, hipStream_t st, const
 
 }  // namespace
 
-size_t conv3_wgrad_slab_bytes(int Cin, int Cout) {
-  // <= 256 workgroups x 8 waves x TPW tiles x 4 KB (the W3Cfg arithmetic for run-time channel counts)
+// Floats per workgroup of the w3slab region (conv_bwd_layout): the covered shapes' from the kernels' own configurations; for
+// every other shape the region keeps the size it has always had (8 waves x TPW tiles x 1024 floats by the W3Cfg arithmetic).
+size_t conv3_wgrad_slab_floats(int Cin, int Cout) {
+  const int shape = conv3_bwd_shape(Cin, Cout, Cout == 240 ? 2 : 1);
+  if (shape) {
+    const size_t a = shape == 1 ? W3Cfg<150, 60, false>::SLABF : shape == 2 ? W3Cfg<60, 60, false>::SLABF : W3Cfg<60, 240, true>::SLABF;
+    const size_t b = conv3x_wgrad_slab_floats(shape);
+    return a > b ? a : b;
+  }
   const int cot = (Cout + 31) / 32, roles = Cout > 64 ? (Cout + 127) / 128 : 1;
   const int ct = (cot + roles - 1) / roles;
-  if (ct <= 0 || 8 % ct) return 256;
+  if (ct <= 0 || 8 % ct) return 0;
   const int wpc = 8 / ct, tpc = 9 * ((Cin + 31) / 32) + 1, tpw = (tpc + wpc - 1) / wpc;
-  return (size_t)256 * 8 * tpw * 4096 + 256;
+  return (size_t)8 * tpw * 1024;
 }
 
 // RDST_ENOTSUP = not one of the covered shapes.  dY in the output geometry (pixel-shuffled when g.r == 2).
-int conv3_wgrad_bf16(const bf16* X, int64_t ldx, int in_act, const bf16* dY, int64_t lddy, float* dW, float* dbias, float* slab,
+int conv3_wgrad_bf16(const bf16* X, int64_t ldx, int in_act, const bf16* dY, int64_t lddy, float* dW, float* dbias, const WsSlab& slab,
                      const ConvGeom& g, float s, hipStream_t st) {
-  if (!conv3_bwd_geom_ok(g, in_act, slab) || !conv3_rows_ok(X, ldx) || !conv3_rows_ok(dY, lddy)) return RDST_ENOTSUP;
+  if (!conv3_bwd_geom_ok(g, in_act, slab.p) || !conv3_rows_ok(X, ldx) || !conv3_rows_ok(dY, lddy)) return RDST_ENOTSUP;
   const int shape = conv3_bwd_shape(g.Cin, g.Cout, g.r);
   if (!shape || (shape == 3 && lddy != 60)) return RDST_ENOTSUP;   // (sub-pixel pairs contiguous in dY)
   const int64_t xb = ((g.pixels() - 1) * ldx + g.Cin) * 2;
   const int64_t yb = ((g.pixels() * g.r * g.r - 1) * lddy + g.Cout / (g.r * g.r)) * 2;
   if (xb >= (1ll << 31) || yb >= (1ll << 31)) return RDST_ENOTSUP;
   W3Args p{};
-  p.X = X; p.ldx = ldx; p.x_bytes = (int)xb; p.dY = dY; p.lddy = lddy; p.dy_bytes = (int)yb; p.slab = slab;
+  p.X = X; p.ldx = ldx; p.x_bytes = (int)xb; p.dY = dY; p.lddy = lddy; p.dy_bytes = (int)yb; p.slab = slab.p;
   p.B = g.B; p.H = g.H; p.W = g.W;
-  if (shape == 1) return launch_w3<150, 60, false>(p, s, dW, dbias, st, "conv3_wgrad_150_60");
-  if (shape == 2) return launch_w3<60, 60, false>(p, s, dW, dbias, st, "conv3_wgrad_60_60");
-  return launch_w3<60, 240, true>(p, s, dW, dbias, st, "conv3_wgrad_60_240_unshuf");
+  if (shape == 1) return launch_w3<150, 60, false>(p, slab, s, dW, dbias, st, "conv3_wgrad_150_60");
+  if (shape == 2) return launch_w3<60, 60, false>(p, slab, s, dW, dbias, st, "conv3_wgrad_60_60");
+  return launch_w3<60, 240, true>(p, slab, s, dW, dbias, st, "conv3_wgrad_60_240_unshuf");
 }

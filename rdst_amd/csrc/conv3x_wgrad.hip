@@ -250,11 +250,12 @@ __global__ void __launch_bounds__(256) conv3x_wgrad_reduce_kernel(const float* _
 }
 
 template <int CI, int CO>
-int launch_w3x(W3XArgs& p, float s, int cmul, int coff, float* dW, float* dbias, hipStream_t st, const char* what) {
+int launch_w3x(W3XArgs& p, const WsSlab& slab, float s, int cmul, int coff, float* dW, float* dbias, hipStream_t st, const char* what) {
   using CF = W3X<CI, CO>;
   Conv3Strips sp;
-  if (!conv3_strip_plan(p.B, p.H, p.W, 2, 256, sp)) return RDST_ENOTSUP;
+  if (!conv3_strip_plan(p.B, p.H, p.W, 2, (int)slab.cap(kCUs, CF::SLABF), sp)) return RDST_ENOTSUP;
   p.SH = sp.SH; p.nys = sp.nys; p.nstrips = sp.nstrips; p.npg = sp.npg;
+  if (int rc = rdst_slab_fits(slab, p.npg, CF::SLABF, what)) return rc;
   auto kern = conv3x_wgrad_kernel<CI, CO>;
   if (int rc = rdst_launch(kern, dim3((unsigned)p.npg), dim3(512), CF::SMEM, st, what, p)) return rc;
   return rdst_launch(conv3x_wgrad_reduce_kernel<CI, CO>, dim3((unsigned)((CF::SLABF + 255) / 256)), dim3(256), 0, st, "conv3x_wgrad_reduce",
@@ -263,24 +264,28 @@ int launch_w3x(W3XArgs& p, float s, int cmul, int coff, float* dW, float* dbias,
 
 }  // namespace
 
-// RDST_ENOTSUP = not one of the covered shapes.  dY in the output geometry (pixel-shuffled when g.r == 2).  slab: conv3_wgrad_slab_bytes.
-int conv3x_wgrad_f32(const float* X, int64_t ldx, int in_act, const float* dY, int64_t lddy, float* dW, float* dbias, float* slab,
+size_t conv3x_wgrad_slab_floats(int shape) {   // (60 -> 240: four launches of the 60 -> 60 kernel)
+  return shape == 1 ? W3X<150, 60>::SLABF : shape == 2 || shape == 3 ? W3X<60, 60>::SLABF : 0;
+}
+
+// RDST_ENOTSUP = not one of the covered shapes.  dY in the output geometry (pixel-shuffled when g.r == 2).  slab: w3slab of conv_bwd_layout.
+int conv3x_wgrad_f32(const float* X, int64_t ldx, int in_act, const float* dY, int64_t lddy, float* dW, float* dbias, const WsSlab& slab,
                      const ConvGeom& g, float s, hipStream_t st) {
-  if (!conv3_bwd_geom_ok(g, in_act, slab) || !conv3_rows_ok(X, ldx) || !conv3_rows_ok(dY, lddy)) return RDST_ENOTSUP;
+  if (!conv3_bwd_geom_ok(g, in_act, slab.p) || !conv3_rows_ok(X, ldx) || !conv3_rows_ok(dY, lddy)) return RDST_ENOTSUP;
   const int shape = conv3_bwd_shape(g.Cin, g.Cout, g.r);
   if (!shape) return RDST_ENOTSUP;
   const int64_t xb = ((g.pixels() - 1) * ldx + g.Cin) * 4;
   const int64_t yb = ((g.pixels() * g.r * g.r - 1) * lddy + g.Cout / (g.r * g.r)) * 4;
   if (xb >= (1ll << 31) || yb >= (1ll << 31)) return RDST_ENOTSUP;
   W3XArgs p{};
-  p.X = X; p.ldx = ldx; p.x_bytes = (int)xb; p.dY = dY; p.lddy = lddy; p.dy_bytes = (int)yb; p.slab = slab;
+  p.X = X; p.ldx = ldx; p.x_bytes = (int)xb; p.dY = dY; p.lddy = lddy; p.dy_bytes = (int)yb; p.slab = slab.p;
   p.B = g.B; p.H = g.H; p.W = g.W; p.ymul = 1; p.yoff = 0; p.xmul = 1; p.xoff = 0;
-  if (shape == 1) return launch_w3x<150, 60>(p, s, 1, 0, dW, dbias, st, "conv3x_wgrad_150_60");
-  if (shape == 2) return launch_w3x<60, 60>(p, s, 1, 0, dW, dbias, st, "conv3x_wgrad_60_60");
+  if (shape == 1) return launch_w3x<150, 60>(p, slab, s, 1, 0, dW, dbias, st, "conv3x_wgrad_150_60");
+  if (shape == 2) return launch_w3x<60, 60>(p, slab, s, 1, 0, dW, dbias, st, "conv3x_wgrad_60_60");
   for (int q = 0; q < 4; ++q) {   // conv channel 4 c' + q is channel c' of output pixel (2y + (q >> 1), 2x + (q & 1))
     W3XArgs pq = p;
     pq.ymul = 2; pq.yoff = q >> 1; pq.xmul = 2; pq.xoff = q & 1;
-    if (int rc = launch_w3x<60, 60>(pq, s, 4, q, dW, dbias, st, "conv3x_wgrad_60_240_q")) return rc;
+    if (int rc = launch_w3x<60, 60>(pq, slab, s, 4, q, dW, dbias, st, "conv3x_wgrad_60_240_q")) return rc;
   }
   return 0;
 }

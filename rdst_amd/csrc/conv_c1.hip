@@ -474,13 +474,10 @@ int conv_c1_fwd_bf16(const bf16* X, int64_t ldx, int in_act, const float* Wc, co
   if (!c1_ok(g, in_act) || R || ((uintptr_t)X & 3) || (ldx & 1)) return RDST_ENOTSUP;
   C1Args p{};
   p.X = X; p.ldx = ldx; p.W = Wc; p.bias = bias; p.Y = Y; p.ldy = ldy; p.g = g; p.s = s;
-  const int grid = c1_grid(p, 512);   // two workgroups per CU (173 registers, 49 KB of LDS)
+  const int grid = c1_grid(p, 2 * kCUs);   // two workgroups per CU (173 registers, 49 KB of LDS)
   hipLaunchKernelGGL(conv_c1_fwd_kernel, dim3(grid), dim3(C1_THREADS), 0, st, p);
   return rdst_launch_status("conv_c1_fwd");
 }
-
-size_t conv_c1_slab_floats(int Cin) { return (size_t)(1024 + 1) * (Cin * 9 + 1); }   // 1024 partial rows + the reduced row
-size_t conv_in1_slab_floats(int Cout) { return (size_t)(1024 + 1) * (Cout * 10); }
 
 // The mirror shape: 3x3 conv from ONE input channel to Cout (the head conv of RDSTSR on a single-channel image), bf16 rows.
 // Forward = conv_c1_dgrad_kernel<true>, weight gradient = conv_c1_wgrad_kernel<true> (no data gradient: the input is the image).
@@ -494,21 +491,23 @@ int conv_in1_fwd_bf16(const bf16* X, int64_t ldx, int in_act, const float* Wc, c
   ConvGeom gm = g;
   gm.Cin = g.Cout; gm.Cout = 1;            // the kernels' view: Cin = the wide side
   p.W = Wc; p.bias = bias; p.dY = X; p.lddy = ldx; p.dX = Y; p.lddx = ldy; p.Acc = R; p.ldacc = ldr; p.g = gm; p.s = s;
-  const int grid = c1_grid(p, 1024);
+  const int grid = c1_grid(p, 4 * kCUs);
   hipLaunchKernelGGL(conv_c1_dgrad_kernel<true>, dim3(grid), dim3(C1_THREADS), 0, st, p);
   return rdst_launch_status("conv_in1_fwd");
 }
-int conv_in1_wgrad_bf16(const bf16* X, int64_t ldx, int in_act, const bf16* dY, int64_t lddy, float* dW, float* dbias, float* slab,
+int conv_in1_wgrad_bf16(const bf16* X, int64_t ldx, int in_act, const bf16* dY, int64_t lddy, float* dW, float* dbias, const WsSlab& ws,
                         const ConvGeom& g, float s, hipStream_t st) {
+  float* const slab = ws.p;
   if (!in1_ok(g, in_act) || ((uintptr_t)dY & 3) || (lddy & 1)) return RDST_ENOTSUP;
   C1Args p{};
   ConvGeom gm = g;
   gm.Cin = g.Cout; gm.Cout = 1;
   p.X = dY; p.ldx = lddy; p.dY = X; p.lddy = ldx; p.g = gm; p.s = s; p.slab = slab;
-  const int grid = c1_grid(p, 1024);
+  const int n = g.Cout * 9, row = n + g.Cout;
+  const int grid = c1_grid(p, (int)ws.cap(kC1Rows + 1, row) - 1);   // (+ the reduced row)
+  if (int rc = rdst_slab_fits(ws, grid + 1, row, "conv_in1_wgrad")) return rc;
   hipLaunchKernelGGL(conv_c1_wgrad_kernel<true>, dim3(grid), dim3(C1_THREADS), 0, st, p);
   if (int rc = rdst_launch_status("conv_in1_wgrad")) return rc;
-  const int n = g.Cout * 9, row = n + g.Cout;
   float* red = slab + (size_t)grid * row;
   if (int rc = slab_reduce(slab, red, grid, row, st)) return rc;
   if (dW) (void)hipMemcpyAsync(dW, red, sizeof(float) * n, hipMemcpyDeviceToDevice, st);
@@ -516,11 +515,12 @@ int conv_in1_wgrad_bf16(const bf16* X, int64_t ldx, int in_act, const bf16* dY, 
   return 0;
 }
 
-// dW (1, Cin, 3, 3), dbias (1), dX (optional) of the one-output-channel conv; slab >= conv_c1_slab_floats()
+// dW (1, Cin, 3, 3), dbias (1), dX (optional) of the one-output-channel conv; slab: c1slab of conv_bwd_layout
 // The weight gradient, its reduce and its two copies go to `wst` (they read X, dY and the slab alone), the data gradient to `st`.
 int conv_c1_bwd_bf16(const bf16* X, int64_t ldx, int in_act, const float* Wc, const bf16* dY, int64_t lddy, bf16* dX,
-                     int64_t lddx, const bf16* acc, int64_t ldacc, float* dW, float* dbias, float* slab, const ConvGeom& g,
+                     int64_t lddx, const bf16* acc, int64_t ldacc, float* dW, float* dbias, const WsSlab& ws, const ConvGeom& g,
                      float s, hipStream_t st, hipStream_t wst) {
+  float* const slab = ws.p;
   if (g.Cin == 1 && g.Cout == 1 && g.ks == 1 && g.r == 1 && in_act == 0 && !dW && !dbias && dX)   // frozen MeanShift: dX = dY w s (+ dX_add)
     return pw11_launch(dY, lddy, Wc, nullptr, acc, ldacc, dX, lddx, g.pixels(), s, st, "conv_pw11_dgrad");
   if (!c1_ok(g, in_act) || ((uintptr_t)X & 3) || (ldx & 1) || ((uintptr_t)dX & 3) || (lddx & 1) || ((uintptr_t)acc & 3) || (ldacc & 1))
@@ -529,10 +529,11 @@ int conv_c1_bwd_bf16(const bf16* X, int64_t ldx, int in_act, const float* Wc, co
   p.X = X; p.ldx = ldx; p.W = Wc; p.dY = dY; p.lddy = lddy; p.dX = dX; p.lddx = lddx; p.Acc = acc; p.ldacc = ldacc;
   p.g = g; p.s = s; p.slab = slab;
   if (dW || dbias) {
-    const int grid = c1_grid(p, 1024);
+    const int n = g.Cin * 9;
+    const int grid = c1_grid(p, (int)ws.cap(kC1Rows + 1, n + 1) - 1);   // (+ the reduced row)
+    if (int rc = rdst_slab_fits(ws, grid + 1, n + 1, "conv_c1_wgrad")) return rc;
     hipLaunchKernelGGL(conv_c1_wgrad_kernel<false>, dim3(grid), dim3(C1_THREADS), 0, wst, p);
     if (int rc = rdst_launch_status("conv_c1_wgrad")) return rc;
-    const int n = g.Cin * 9;
     // one reduction over [grid][n + 1]: dW then dbias are contiguous in the slab row; the destinations are not
     float* red = slab + (size_t)grid * (n + 1);
     if (int rc = slab_reduce(slab, red, grid, n + 1, wst)) return rc;
@@ -540,7 +541,7 @@ int conv_c1_bwd_bf16(const bf16* X, int64_t ldx, int in_act, const float* Wc, co
     if (dbias) (void)hipMemcpyAsync(dbias, red + n, sizeof(float), hipMemcpyDeviceToDevice, wst);
   }
   if (dX) {
-    const int grid = c1_grid(p, 1024);
+    const int grid = c1_grid(p, 4 * kCUs);
     hipLaunchKernelGGL(conv_c1_dgrad_kernel<false>, dim3(grid), dim3(C1_THREADS), 0, st, p);
     if (int rc = rdst_launch_status("conv_c1_dgrad")) return rc;
   }

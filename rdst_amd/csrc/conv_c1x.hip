@@ -269,16 +269,18 @@ template <int C>
 int run_fwd(C1XArgs& p, hipStream_t st) {
   p.tiles_y = (p.H + TH1 - 1) / TH1;   // (this kernel's tiles are 4 rows high)
   p.ntiles = (int64_t)p.B * p.tiles_x * p.tiles_y;
-  return rdst_launch(c1x_fwd_kernel<C>, dim3(grid_of(p, 768)), dim3(NTHR), fwd_smem<C>(), st, "c1x_fwd", p);
+  return rdst_launch(c1x_fwd_kernel<C>, dim3(grid_of(p, 3 * kCUs)), dim3(NTHR), fwd_smem<C>(), st, "c1x_fwd", p);
 }
 template <int C>
 int run_wide(C1XArgs& p, hipStream_t st) {
-  hipLaunchKernelGGL(c1x_wide_kernel<C>, dim3(grid_of(p, 1024)), dim3(NTHR), 0, st, p);
+  hipLaunchKernelGGL(c1x_wide_kernel<C>, dim3(grid_of(p, 4 * kCUs)), dim3(NTHR), 0, st, p);
   return rdst_launch_status("c1x_wide");
 }
 template <int C>
-int run_wgrad(C1XArgs& p, float* dW, float* dbias, int wsc, int wst, int bias_wide, hipStream_t st) {
-  const int grid = grid_of(p, 256), ROW = 10 * C + 1;
+int run_wgrad(C1XArgs& p, const WsSlab& ws, float* dW, float* dbias, int wsc, int wst, int bias_wide, hipStream_t st) {
+  const int ROW = 10 * C + 1, grid = grid_of(p, (int)ws.cap(kCUs + 1, ROW) - 1);   // (+ the reduced row)
+  if (int rc = rdst_slab_fits(ws, grid + 1, ROW, "c1x_wgrad")) return rc;
+  p.slab = ws.p;
   if (int rc = rdst_launch(c1x_wgrad_kernel<C>, dim3(grid), dim3(NTHR), wg_smem<C>(), st, "c1x_wgrad", p)) return rc;
   float* red = p.slab + (size_t)grid * ROW;
   if (int rc = slab_reduce(p.slab, red, grid, ROW, st)) return rc;
@@ -319,8 +321,6 @@ int pw11x_launch(const float* in, int64_t ldi, const float* W, const float* bias
 }
 }  // namespace
 
-size_t conv_c1x_slab_floats(int C) { return (size_t)(256 + 1) * (10 * C + 1); }
-
 // wide -> 1 forward (the tail conv).  RDST_ENOTSUP for other shapes / a residual.
 int conv_c1x_fwd_f32(const float* X, int64_t ldx, int in_act, const float* Wc, const float* bias, const float* R, int64_t ldr, float* Y,
                      int64_t ldy, const ConvGeom& g, float s, hipStream_t st) {
@@ -344,9 +344,9 @@ int conv_in1x_fwd_f32(const float* X, int64_t ldx, int in_act, const float* Wc, 
   switch (g.Cout) { case 60: return run_wide<60>(p, st); case 48: return run_wide<48>(p, st); case 64: return run_wide<64>(p, st); }
   return RDST_ENOTSUP;
 }
-// backward of the tail conv (Cout == 1): dX (optional) = s conv^T(dY) + dX_add, dW (1, Cin, 3, 3), dbias (1); slab: conv_c1x_slab_floats(Cin)
+// backward of the tail conv (Cout == 1): dX (optional) = s conv^T(dY) + dX_add, dW (1, Cin, 3, 3), dbias (1); slab: c1slab of conv_bwd_layout
 int conv_c1x_bwd_f32(const float* X, int64_t ldx, int in_act, const float* Wc, const float* dY, int64_t lddy, float* dX, int64_t lddx,
-                     const float* acc, int64_t ldacc, float* dW, float* dbias, float* slab, const ConvGeom& g, float s, hipStream_t st) {
+                     const float* acc, int64_t ldacc, float* dW, float* dbias, const WsSlab& slab, const ConvGeom& g, float s, hipStream_t st) {
   if (g.Cin == 1 && g.Cout == 1 && g.ks == 1 && g.r == 1 && in_act == 0 && !dW && !dbias && dX)   // frozen MeanShift: dX = dY w s (+ dX_add)
     return pw11x_launch(dY, lddy, Wc, nullptr, acc, ldacc, dX, lddx, g.pixels(), s, st, "conv_pw11x_dgrad");
   if (g.Cout != 1 || !shape_ok(g, in_act, g.Cin) || ((uintptr_t)X & 3) || ((uintptr_t)dX & 3) || ((uintptr_t)acc & 3)) return RDST_ENOTSUP;
@@ -354,11 +354,11 @@ int conv_c1x_bwd_f32(const float* X, int64_t ldx, int in_act, const float* Wc, c
   set_tiles(p, g, g.Cin);
   p.s = s;
   if (dW || dbias) {
-    p.Xw = X; p.ldw = ldx; p.X1 = dY; p.ld1 = lddy; p.slab = slab; p.mirror = 0;
+    p.Xw = X; p.ldw = ldx; p.X1 = dY; p.ld1 = lddy; p.mirror = 0;
     const int C = g.Cin;
-    if (C == 60) { if (int rc = run_wgrad<60>(p, dW, dbias, 9, 1, 0, st)) return rc; }
-    else if (C == 48) { if (int rc = run_wgrad<48>(p, dW, dbias, 9, 1, 0, st)) return rc; }
-    else { if (int rc = run_wgrad<64>(p, dW, dbias, 9, 1, 0, st)) return rc; }
+    if (C == 60) { if (int rc = run_wgrad<60>(p, slab, dW, dbias, 9, 1, 0, st)) return rc; }
+    else if (C == 48) { if (int rc = run_wgrad<48>(p, slab, dW, dbias, 9, 1, 0, st)) return rc; }
+    else { if (int rc = run_wgrad<64>(p, slab, dW, dbias, 9, 1, 0, st)) return rc; }
   }
   if (dX) {
     C1XArgs q{};
@@ -370,15 +370,15 @@ int conv_c1x_bwd_f32(const float* X, int64_t ldx, int in_act, const float* Wc, c
   return 0;
 }
 // weight gradient of the head conv (Cin == 1, no data gradient: the input is the image): dW (Cout, 1, 3, 3), dbias (Cout)
-int conv_in1x_wgrad_f32(const float* X, int64_t ldx, int in_act, const float* dY, int64_t lddy, float* dW, float* dbias, float* slab,
+int conv_in1x_wgrad_f32(const float* X, int64_t ldx, int in_act, const float* dY, int64_t lddy, float* dW, float* dbias, const WsSlab& slab,
                         const ConvGeom& g, float s, hipStream_t st) {
   if (g.Cin != 1 || !shape_ok(g, in_act, g.Cout) || ((uintptr_t)dY & 3)) return RDST_ENOTSUP;
   C1XArgs p{};
   set_tiles(p, g, g.Cout);
   // dW[c][t] = sum_p dY[p][c] x[p + t - centre] = sum_q x[q] dY[q - (t - centre)][c]: the wide tensor (dY) shifted the other way
-  p.Xw = dY; p.ldw = lddy; p.X1 = X; p.ld1 = ldx; p.slab = slab; p.s = s; p.mirror = 1;
+  p.Xw = dY; p.ldw = lddy; p.X1 = X; p.ld1 = ldx; p.s = s; p.mirror = 1;
   const int C = g.Cout;
-  if (C == 60) return run_wgrad<60>(p, dW, dbias, 9, 1, 1, st);
-  if (C == 48) return run_wgrad<48>(p, dW, dbias, 9, 1, 1, st);
-  return run_wgrad<64>(p, dW, dbias, 9, 1, 1, st);
+  if (C == 60) return run_wgrad<60>(p, slab, dW, dbias, 9, 1, 1, st);
+  if (C == 48) return run_wgrad<48>(p, slab, dW, dbias, 9, 1, 1, st);
+  return run_wgrad<64>(p, slab, dW, dbias, 9, 1, 1, st);
 }

@@ -504,7 +504,7 @@ int launch_conv_rows(ConvArgs<T>& p, bool split, hipStream_t st, const char* wha
   const size_t smem = (size_t)p.eps_off + extra;
   const int64_t nslabs = g.pixels() / 32;
   int64_t grid = (nslabs + 7) / 8;
-  if (grid > 256) grid = 256;
+  if (grid > kCUs) grid = kCUs;
   static int pf = -1;
   if (pf < 0) { const char* e = rdst_dbg_getenv("RDST_CONV_PF"); pf = e ? atoi(e) : 3; }
   auto kern = pf == 1 ? conv_rows_kernel<T, MODE, 1> : pf == 2 ? conv_rows_kernel<T, MODE, 2> : conv_rows_kernel<T, MODE, 3>;
@@ -539,7 +539,7 @@ int launch_conv(ConvArgs<T>& p, bool split, hipStream_t st, const char* what) {
   const size_t smem = (size_t)ntap * nch * p.ldw + (rows ? 8 * 4096 : 0);
   const int64_t nslabs = (p.g.pixels() + 31) / 32;
   int64_t grid = (nslabs + 7) / 8;
-  if (grid > 256) grid = 256;
+  if (grid > kCUs) grid = kCUs;
   int rc = 0;
 #define RDST_CONV_LAUNCH(TM)                                                                                         \
   {                                                                                                                  \
@@ -1116,14 +1116,6 @@ int conv_fwd_mfma(const T* X, int64_t ldx, int in_act, const float* Wc, const fl
   return 0;
 }
 
-size_t conv_mfma_scratch_bytes(const ConvGeom& g) {
-  // un-shuffled dY (bf16 or fp32) + wgrad slab
-  const size_t unsh = g.r > 1 ? (size_t)g.pixels() * g.Cout * 4 : 0;
-  const int CinP = ((g.Cin + 1 + 31) / 32) * 32;
-  const size_t slab = (size_t)128 * g.ks * g.Cout * g.ks * CinP * sizeof(float);
-  return unsh + slab + 256;
-}
-
 template <typename T>
 const T* plain_dy(const T* dY, int64_t lddy, const ConvGeom& g, void* scratch, int64_t& ld_out, hipStream_t st, int& rc) {
   rc = 0;
@@ -1173,14 +1165,15 @@ int conv_dgrad_mfma(const T* X, int64_t ldx, int in_act, const float* Wc, const 
 
 template <typename T>
 int conv_wgrad_mfma(const T* X, int64_t ldx, int in_act, const T* dYp, int64_t lddyp, float* dW, float* dbias,
-                    float* slab, const ConvGeom& g, float s, bool split, hipStream_t st) {
+                    const WsSlab& slab, const ConvGeom& g, float s, bool split, hipStream_t st) {
   if (mfma_disabled() || !rows_ok<T>(X, ldx) || !rows_ok<T>(dYp, lddyp)) return RDST_ENOTSUP;
   ConvWgradArgs<T> p{};
-  p.X = X; p.ldx = ldx; p.in_act = in_act; p.dY = dYp; p.lddy = lddyp; p.slab = slab; p.g = g;
+  p.X = X; p.ldx = ldx; p.in_act = in_act; p.dY = dYp; p.lddy = lddyp; p.slab = slab.p; p.g = g;
   p.NT = (g.Cout + 31) / 32;
   p.KT = (g.Cin + 1 + 31) / 32;   // room for the ones column
   p.CinP = p.KT * 32;
   p.ones_col = g.Cin;
+  const int64_t per_m = (int64_t)g.ks * g.Cout * g.ks * p.CinP;   // floats per pixel group: the slab's row
   if (p.NT * g.ks * p.KT > 8 * CW_MAXT) return RDST_ENOTSUP;
   // RDST_F32X3: the pipelined kernel's split form
   split = sizeof(T) == 4 && split && g.ks == 3 && g.pad == 1 && g.W % CW_STRIPE == 0;
@@ -1205,10 +1198,11 @@ int conv_wgrad_mfma(const T* X, int64_t ldx, int in_act, const T* dYp, int64_t l
                              : (!((uintptr_t)dYp & 3) && (lddyp * sizeof(T)) % 4 == 0 && (g.Cout * sizeof(T)) % 4 == 0)) &&
                     smem2 <= 160 * 1024;
     if (ok) {
-      int64_t nm = 85;   // x 3 kernel rows = 255 workgroups: one per CU
+      int64_t nm = slab.cap(kCUs / 3, per_m);   // x 3 kernel rows = 255 workgroups: one per CU
       if (nm > (P + SLr - 1) / SLr) nm = (P + SLr - 1) / SLr;
       p.pix_per_wg = (((P + nm - 1) / nm + SLr - 1) / SLr) * SLr;
       nm = (P + p.pix_per_wg - 1) / p.pix_per_wg;
+      if (int rc = rdst_slab_fits(slab, nm, per_m, "conv_wgrad_rows")) return rc;
       constexpr int PF = sizeof(T) == 2 ? 2 : 1;
       int rc = 0;
 #define RDST_CR_LAUNCH(XF)                                                                                            \
@@ -1221,8 +1215,7 @@ int conv_wgrad_mfma(const T* X, int64_t ldx, int in_act, const T* dYp, int64_t l
       if (in_act) RDST_CR_LAUNCH(3) else RDST_CR_LAUNCH(0)
 #undef RDST_CR_LAUNCH
       if (rc) return rc;
-      const int64_t per_m = (int64_t)g.ks * g.Cout * g.ks * p.CinP;
-      hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)((per_m + 255) / 256)), dim3(256), 0, st, slab, (int)nm, g,
+      hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)((per_m + 255) / 256)), dim3(256), 0, st, slab.p, (int)nm, g,
                          p.CinP, p.ones_col, s, dW, dbias);
       return rdst_launch_status("conv_wgrad_reduce");
     }
@@ -1230,14 +1223,14 @@ int conv_wgrad_mfma(const T* X, int64_t ldx, int in_act, const T* dYp, int64_t l
   const size_t smem = (size_t)CW_STRIPE * (p.ldn + (size_t)g.ks * p.ldk);
   if (smem > 160 * 1024) return RDST_ENOTSUP;
   int64_t nm = (P + CW_STRIPE - 1) / CW_STRIPE;
-  const int64_t cap = 128;
+  const int64_t cap = slab.cap(kConvWgradRows, per_m);
   if (nm > cap) nm = cap;
   p.pix_per_wg = (((P + nm - 1) / nm + CW_STRIPE - 1) / CW_STRIPE) * CW_STRIPE;
   nm = (P + p.pix_per_wg - 1) / p.pix_per_wg;
+  if (int rc = rdst_slab_fits(slab, nm, per_m, "conv_wgrad_mfma")) return rc;
   auto kern = conv_wgrad_mfma_kernel<T>;
   if (int rc = rdst_launch(kern, dim3((unsigned)nm, (unsigned)g.ks), dim3(512), smem, st, "conv_wgrad_mfma", p)) return rc;
-  const int64_t per_m = (int64_t)g.ks * g.Cout * g.ks * p.CinP;
-  hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)((per_m + 255) / 256)), dim3(256), 0, st, slab, (int)nm, g,
+  hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)((per_m + 255) / 256)), dim3(256), 0, st, slab.p, (int)nm, g,
                      p.CinP, p.ones_col, s, dW, dbias);
   return rdst_launch_status("conv_wgrad_reduce");
 }
@@ -1247,7 +1240,7 @@ int conv_wgrad_mfma(const T* X, int64_t ldx, int in_act, const T* dYp, int64_t l
                                 const ConvGeom&, float, bool, hipStream_t);                                          \
   template int conv_dgrad_mfma<T>(const T*, int64_t, int, const float*, const T*, int64_t, T*, int64_t, const T*,    \
                                   int64_t, const ConvGeom&, float, bool, hipStream_t);                               \
-  template int conv_wgrad_mfma<T>(const T*, int64_t, int, const T*, int64_t, float*, float*, float*, const ConvGeom&, \
+  template int conv_wgrad_mfma<T>(const T*, int64_t, int, const T*, int64_t, float*, float*, const WsSlab&, const ConvGeom&, \
                                   float, bool, hipStream_t);                                                         \
   template const T* plain_dy<T>(const T*, int64_t, const ConvGeom&, void*, int64_t&, hipStream_t, int&);
 INST(float)

@@ -115,9 +115,10 @@ __global__ void __launch_bounds__(256) colsum_kernel(F f, int64_t M, int N, floa
 }
 
 template <class F>
-static inline int colsum_launch(const F& f, int64_t M, int N, float* slab, int blocks, float* out, hipStream_t st,
-                                const char* what) {
-  hipLaunchKernelGGL((colsum_kernel<F>), dim3(blocks), dim3(256), 0, st, f, M, N, slab);
+static inline int colsum_launch(const F& f, int64_t M, int N, const WsSlab& slab, float* out, hipStream_t st, const char* what) {
+  const int blocks = (int)slab.cap(kSmallBlocks, N);
+  if (int rc = rdst_slab_fits(slab, blocks, N, what)) return rc;
+  hipLaunchKernelGGL((colsum_kernel<F>), dim3(blocks), dim3(256), 0, st, f, M, N, slab.p);
   if (int rc = rdst_launch_status(what)) return rc;
-  return slab_reduce(slab, out, blocks, N, st);
+  return slab_reduce(slab.p, out, blocks, N, st);
 }

@@ -419,14 +419,6 @@ ln_bwd_rows_kernel(const float* __restrict__ dA, const T* __restrict__ X, int64_
   }
 }
 
-constexpr int kWgradSplits = 96;
-constexpr int kSmallBlocks = 512;
-
-size_t slab_floats(int64_t M, int K, int N) {
-  const size_t a = (size_t)kWgradSplits * N * K, b = linear_wgrad_mfma_slab_floats(M, K, N);
-  return a > b ? a : b;
-}
-
 template <typename T>
 int fwd_t(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, int in_act, const float* Wt, const float* bias,
           const T* R, int64_t ldr, T* Y, int64_t ldy, float* stats, int64_t M, int K, int N, float s, bool split, hipStream_t st) {
@@ -464,22 +456,22 @@ int bwd_t(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, const f
           const T* dY, int64_t lddy, T* dX, int64_t lddx, const T* acc, int64_t ldacc, float* dW, float* dbias,
           float* dln_w,
           float* dln_b, float* wsp, int64_t M, int K, int N, float s, bool split, hipStream_t st, const T* acc2, int64_t ldacc2) {
-  // workspace carve: [dA: M*K] [slabW: splits*N*K] [small: kSmallBlocks * max(N, 2K)]
-  float* dA = wsp;
-  float* slabW = dA + (ln_w ? M * K : 0);
-  float* small = slabW + slab_floats(M, K, N);
+  const LinBwdWs w = lin_bwd_layout(wsp, M, K, N, ln_w != nullptr, true);
+  float* const dA = w.dA;
+  const WsSlab& slabW = w.slabW;
+  const WsSlab& small = w.small;
   if constexpr (sizeof(T) == 4) {   // RDST_F32X3: the one-pass kernel of the E1 shapes (every gradient requested), else the paths below
-    if (split && Wt && dX && dW && dbias && (!ln_w || (dln_w && dln_b && (int64_t)N * (K + 1) <= M * K)) && !rdst_dbg_getenv("RDST_LBX_OFF")) {
+    if (split && Wt && dX && dW && dbias && (!ln_w || (dln_w && dln_b && w.G)) && !rdst_dbg_getenv("RDST_LBX_OFF")) {
       const int rc = lnlin3x_bwd_f32(X, ldx, ln_w, ln_b, stats, in_act, Wt, dY, lddy, dX, lddx, acc, ldacc, acc2, ldacc2, dW, dbias, dln_w,
-                                     dln_b, slabW, dA, M, K, N, s, st);
+                                     dln_b, slabW, w.G, M, K, N, s, st);
       if (rc != RDST_ENOTSUP) return rc;
     }
   }
   if (acc2) {   // a second addend of dX: only the one-pass LayerNorm-Linear backward of the E1 shapes takes it (nothing is launched otherwise)
     if constexpr (sizeof(T) == 2) {
-      if (Wt && ln_w && ln_b && dW && dbias && dln_w && dln_b && dX && K <= 128 && (int64_t)N * (K + 1) <= M * K)
+      if (Wt && ln_w && ln_b && dW && dbias && dln_w && dln_b && dX && K <= 128 && w.G)
         return linear_ln_bwd_fused_bf16(X, ldx, ln_w, ln_b, stats, Wt, dY, lddy, dX, lddx, acc, ldacc, dW, dbias, dln_w, dln_b, slabW,
-                                        dA, M, K, N, s, st, acc2, ldacc2);
+                                        w.G, M, K, N, s, st, acc2, ldacc2);
     }
     return RDST_ENOTSUP;
   }
@@ -488,8 +480,7 @@ int bwd_t(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, const f
     // LayerNorm-fused Linear with everything requested in one call: the weight-gradient pass runs on x-hat and
     // its reduction also yields d(gamma)/d(beta); the data-gradient kernel then only produces dX.
     if (ln_w && ln_b && dW && dbias && dln_w && dln_b && dX && K <= 128 && !rdst_dbg_getenv("RDST_LN_BWD_V1")) {
-      float* G = dA;   // the fp32 dA buffer of the generic path is unused here: N*(K+1) <= M*K floats of scratch
-      if ((int64_t)N * (K + 1) <= M * K) {
+      if (float* G = w.G) {   // the fp32 dA buffer of the generic path is unused here: N*(K+1) floats of scratch where they fit
         if constexpr (sizeof(T) == 2) {   // one pass over (x, dY) for everything, where the shape is covered
           const int rcf = linear_ln_bwd_fused_bf16(X, ldx, ln_w, ln_b, stats, Wt, dY, lddy, dX, lddx, acc, ldacc, dW, dbias, dln_w,
                                                    dln_b, slabW, G, M, K, N, s, st);
@@ -537,22 +528,23 @@ int bwd_t(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, const f
     }
     if (!wgrad_done && dbias) {
       DyCol<T> f{dY, lddy, s};
-      if (int rc = colsum_launch(f, M, N, small, kSmallBlocks, dbias, st, "linear_dbias")) return rc;
+      if (int rc = colsum_launch(f, M, N, small, dbias, st, "linear_dbias")) return rc;
     }
     if (!wgrad_done && dW) {
       DyAT<T> la{dY, lddy, s};
       LinInT<T> lb{fin};
-      SlabEp ep{slabW, (int64_t)N * K, K};
-      const int z = gemm_valu_splits(M, kWgradSplits);
-      if (int rc2 = gemm_valu_launch(la, lb, ep, N, K, M, kWgradSplits, st, "linear_wgrad")) return rc2;
-      if (int rc2 = slab_reduce(slabW, dW, z, (int64_t)N * K, st)) return rc2;
+      SlabEp ep{slabW.p, (int64_t)N * K, K};
+      const int z = gemm_valu_splits(M, kLinWgradSplits);
+      if (int rc2 = rdst_slab_fits(slabW, z, (int64_t)N * K, "linear_wgrad")) return rc2;
+      if (int rc2 = gemm_valu_launch(la, lb, ep, N, K, M, kLinWgradSplits, st, "linear_wgrad")) return rc2;
+      if (int rc2 = slab_reduce(slabW.p, dW, z, (int64_t)N * K, st)) return rc2;
     }
     if (dX && ln_w) {  // fused dgrad + LayerNorm backward
       int nslab = 0;
       const int rc = linear_dgrad_ln_mfma<T>(X, ldx, stats, ln_w, Wt, dY, lddy, dX, lddx, acc, ldacc, small, &nslab, M, K,
                                              N, s, st);
       if (rc == 0) {
-        return slab_reduce2(small, dln_w, dln_b, nslab, K, st);
+        return slab_reduce2(small.p, dln_w, dln_b, nslab, K, st);
       }
       if (rc != RDST_ENOTSUP) return rc;
     }
@@ -578,16 +570,17 @@ int bwd_t(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, const f
     const float* dAsrc = dA;
     if (!dX && !dln_w && !dln_b) return 0;
     if (K > 512) return rdst_fail(RDST_ENOTSUP, "rdst_ln_linear_bwd: LayerNorm width %d > 512", K);
-    const int blocks = (int)((M + 3) / 4 < kSmallBlocks ? (M + 3) / 4 : kSmallBlocks);
+    const int blocks = (int)small.cap((M + 3) / 4 < kSmallBlocks ? (M + 3) / 4 : kSmallBlocks, 2 * K);
+    if (int rc = rdst_slab_fits(small, blocks, 2 * K, "ln_bwd_rows")) return rc;
     const int kc = (K + 63) / 64;
 #define RDST_LNB(KC)                                                                                              \
   hipLaunchKernelGGL((ln_bwd_rows_kernel<T, KC>), dim3(blocks), dim3(256), 0, st, dAsrc, X, ldx, stats, ln_w, dX, \
-                     lddx, acc, ldacc, small, M, K)
+                     lddx, acc, ldacc, small.p, M, K)
     if (kc <= 1) RDST_LNB(1); else if (kc <= 2) RDST_LNB(2); else if (kc <= 4) RDST_LNB(4); else RDST_LNB(8);
 #undef RDST_LNB
     if (int rc = rdst_launch_status("ln_bwd_rows")) return rc;
     // slab is [blocks][2][K] -> reduce to a [2][K] scratch then copy out
-    if (int rc = slab_reduce2(small, dln_w, dln_b, blocks, K, st)) return rc;
+    if (int rc = slab_reduce2(small.p, dln_w, dln_b, blocks, K, st)) return rc;
   }
   return 0;
 }
@@ -606,28 +599,31 @@ template <typename T>
 int ln_only_bwd(const T* X, int64_t ldx, const float* ln_w, const float* stats, const T* dY, int64_t lddy, T* dX,
                 int64_t lddx, const T* acc, int64_t ldacc, float* dln_w, float* dln_b, float* wsp, int64_t M, int K, float s,
                 hipStream_t st) {
-  float* dA = wsp;
-  float* small = dA + M * K;
+  const LinBwdWs w = lin_bwd_layout(wsp, M, K, K, true, false);
+  float* const dA = w.dA;
+  const WsSlab& small = w.small;
   const int64_t n = M * K;
   if (K <= 64 && ln8_ok(X, ldx, dY, lddy, dX, lddx, K, (int)sizeof(T)) && ln8_ok(acc, ldacc, nullptr, 0, nullptr, 0, K, (int)sizeof(T))) {
     const int64_t nb = (M + 31) / 32;
-    const int blocks = (int)(nb < kSmallBlocks ? nb : kSmallBlocks);
-    hipLaunchKernelGGL((ln8_bwd_kernel<T>), dim3(blocks), dim3(256), 0, st, dY, lddy, X, ldx, stats, ln_w, dX, lddx, acc, ldacc, small, M, K, s);
+    const int blocks = (int)small.cap(nb < kSmallBlocks ? nb : kSmallBlocks, 2 * K);
+    if (int rc = rdst_slab_fits(small, blocks, 2 * K, "ln8_bwd")) return rc;
+    hipLaunchKernelGGL((ln8_bwd_kernel<T>), dim3(blocks), dim3(256), 0, st, dY, lddy, X, ldx, stats, ln_w, dX, lddx, acc, ldacc, small.p, M, K, s);
     if (int rc = rdst_launch_status("ln8_bwd")) return rc;
-    return slab_reduce2(small, dln_w, dln_b, blocks, K, st);
+    return slab_reduce2(small.p, dln_w, dln_b, blocks, K, st);
   }
   hipLaunchKernelGGL((scale_to_f32_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dY, lddy, dA, M, K, s);
   if (int rc = rdst_launch_status("scale_to_f32")) return rc;
   if (K > 512) return rdst_fail(RDST_ENOTSUP, "rdst_ln_linear_bwd: LayerNorm width %d > 512", K);
-  const int blocks = (int)((M + 3) / 4 < kSmallBlocks ? (M + 3) / 4 : kSmallBlocks);
+  const int blocks = (int)small.cap((M + 3) / 4 < kSmallBlocks ? (M + 3) / 4 : kSmallBlocks, 2 * K);
+  if (int rc = rdst_slab_fits(small, blocks, 2 * K, "ln_bwd_rows")) return rc;
   const int kc = (K + 63) / 64;
 #define RDST_LNB(KC)                                                                                           \
   hipLaunchKernelGGL((ln_bwd_rows_kernel<T, KC>), dim3(blocks), dim3(256), 0, st, dA, X, ldx, stats, ln_w, dX, \
-                     lddx, acc, ldacc, small, M, K)
+                     lddx, acc, ldacc, small.p, M, K)
   if (kc <= 1) RDST_LNB(1); else if (kc <= 2) RDST_LNB(2); else if (kc <= 4) RDST_LNB(4); else RDST_LNB(8);
 #undef RDST_LNB
   if (int rc = rdst_launch_status("ln_bwd_rows")) return rc;
-  return slab_reduce2(small, dln_w, dln_b, blocks, K, st);
+  return slab_reduce2(small.p, dln_w, dln_b, blocks, K, st);
 }
 
 }  // namespace
@@ -682,8 +678,7 @@ extern "C" int rdst_ln_linear_fwd(const void* X, int64_t ld_x, const float* ln_w
 
 extern "C" size_t rdst_ln_linear_bwd_workspace(int64_t M, int K, int N) {
   if (M <= 0 || K <= 0 || N <= 0) return 0;
-  const size_t mx = (size_t)(N > 2 * K ? N : 2 * K);
-  return sizeof(float) * ((size_t)M * K + slab_floats(M, K, N) + (size_t)kSmallBlocks * mx + 2 * (size_t)K + 64);
+  return lin_bwd_layout(nullptr, M, K, N, true, true).bytes;
 }
 
 namespace {

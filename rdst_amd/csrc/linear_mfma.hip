@@ -740,7 +740,7 @@ int launch_lin(LinArgs<T>& p, bool split, hipStream_t st, const char* what) {
   if (smem > 160 * 1024) return RDST_ENOTSUP;
   const int64_t nslabs = (p.M + 31) / 32;
   int64_t grid = (nslabs + 7) / 8;
-  int64_t cap = 256;  // persistent: one 8-wave workgroup per CU (the kernel's register count admits no second one)
+  int64_t cap = kCUs;  // persistent: one 8-wave workgroup per CU (the kernel's register count admits no second one)
   { const char* e = rdst_dbg_getenv("RDST_LIN_GRID"); if (e && atoi(e) > 0) cap = atoi(e); }
   if (grid > cap) grid = cap;
   p.stamps = rdst_stamps_begin("RDST_LIN_STAMPS", grid, 16, st);
@@ -1343,13 +1343,13 @@ int linear_dgrad_mfma(const T* X, int64_t ldx, bool has_ln, int in_act, const fl
 // dgrad + LayerNorm backward in one kernel; writes dX and a [*nslab][2][K] slab of d(gamma)/d(beta) partials
 template <typename T>
 int linear_dgrad_ln_mfma(const T* X, int64_t ldx, const float* stats, const float* gamma, const float* Wt, const T* dY,
-                         int64_t lddy, T* dX, int64_t lddx, const T* acc, int64_t ldacc, float* slab, int* nslab,
+                         int64_t lddy, T* dX, int64_t lddx, const T* acc, int64_t ldacc, const WsSlab& slab, int* nslab,
                          int64_t M, int K, int N, float s, hipStream_t st) {
   using MM = Mma<T>;
   if (mfma_disabled() || K > 128 || !dX) return RDST_ENOTSUP;
   LnDgradArgs<T> p{};
   p.dY = dY; p.lddy = lddy; p.Wt = Wt; p.N = N; p.K = K; p.X = X; p.ldx = ldx; p.stats = stats; p.gamma = gamma;
-  p.dX = dX; p.lddx = lddx; p.Acc = acc; p.ldacc = ldacc; p.slab = slab; p.M = M; p.s = s;
+  p.dX = dX; p.lddx = lddx; p.Acc = acc; p.ldacc = ldacc; p.slab = slab.p; p.M = M; p.s = s;
   p.Tn = (N + MM::KP - 1) / MM::KP;
   if (p.Tn > 32) return RDST_ENOTSUP;
   p.ldw = lds_row_bytes(N, sizeof(T));
@@ -1358,8 +1358,9 @@ int linear_dgrad_ln_mfma(const T* X, int64_t ldx, const float* stats, const floa
   if (smem > 160 * 1024) return RDST_ENOTSUP;
   const int64_t nslabs = (M + 31) / 32;
   int64_t grid = (nslabs + 7) / 8;
-  const int64_t cap = 256;   // persistent, one workgroup per CU (185+ VGPRs: a second one would not be resident anyway)
+  const int64_t cap = slab.cap(kCUs, 2 * K);   // persistent, one workgroup per CU (185+ VGPRs: a second one would not be resident anyway)
   if (grid > cap) grid = cap;
+  if (int rc = rdst_slab_fits(slab, grid, 2 * K, "lin_dgrad_ln_mfma")) return rc;
   *nslab = (int)grid;
   int rc = 0;
 #define RDST_LND_LAUNCH(TM)                                                                                          \
@@ -1372,23 +1373,16 @@ int linear_dgrad_ln_mfma(const T* X, int64_t ldx, const float* stats, const floa
   return rc;
 }
 
-size_t linear_wgrad_mfma_slab_floats(int64_t M, int K, int N) {
-  (void)M;
-  // 256 workgroups, or up to 1024 small ones for the narrow projections (linear_ln_bwd_fused_bf16)
-  return (size_t)linear_wgrad_max_wgs(N) * N * (K + 1);
-}
-int linear_wgrad_max_wgs(int N) { return N <= 128 ? 1024 : N <= 192 ? 512 : 256; }
-
 namespace {
 template <typename T>
 int wgrad_impl(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, const float* stats, int in_act,
-               const T* dY, int64_t lddy, float* dW, float* dbias, float* slab, int64_t M, int K, int N, float s,
+               const T* dY, int64_t lddy, float* dW, float* dbias, const WsSlab& slab, int64_t M, int K, int N, float s,
                const float* Wt_fin, float* G, float* dln_w, float* dln_b, bool split, hipStream_t st) {
   const bool lnfin = G != nullptr;   // LayerNorm finish: x-hat slabs, then dW/dbias/d(gamma)/d(beta) from G
   if (mfma_disabled() || !rows_ok<T>(X, ldx) || !rows_ok<T>(dY, lddy)) return RDST_ENOTSUP;
   WgradArgs<T> p{};
   p.X = X; p.ldx = ldx; p.lnw = ln_w; p.lnb = ln_b; p.stats = stats; p.in_act = in_act; p.dY = dY; p.lddy = lddy;
-  p.slab = slab; p.M = M; p.K = K; p.N = N; p.Kx = K + 1;
+  p.slab = slab.p; p.M = M; p.K = K; p.N = N; p.Kx = K + 1;
   p.NT = (N + 31) / 32; p.KT = (p.Kx + 31) / 32;
   if (p.NT * p.KT > WG_WAVES * WG_MAXT || p.NT > 12 || p.KT > 8) return RDST_ENOTSUP;
   // the kernel moves whole 16-B packs: dword-aligned rows and at least one pack per row
@@ -1409,7 +1403,9 @@ int wgrad_impl(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, co
   const size_t smem = (size_t)2 * WG_STRIPE * (p.ldn + p.ldk) + (size_t)2 * p.KT * 32 * sizeof(float);
   if (smem > 160 * 1024) return RDST_ENOTSUP;
   int stripes_per_wg;
-  const int64_t nwg = rdst_tile_grid((M + WG_STRIPE - 1) / WG_STRIPE, 256, &stripes_per_wg);
+  const int tot = N * p.Kx;   // floats per workgroup slab
+  const int64_t nwg = rdst_tile_grid((M + WG_STRIPE - 1) / WG_STRIPE, slab.cap(kCUs, tot), &stripes_per_wg);
+  if (int rc = rdst_slab_fits(slab, nwg, tot, "lin_wgrad_mfma")) return rc;
   p.rows_per_wg = (int64_t)stripes_per_wg * WG_STRIPE;
   constexpr int PF = sizeof(T) == 2 ? 2 : 1;  // register sets of prefetched stripes
   const int xf = lnfin ? 4 : ln_w ? 1 : in_act == RDST_ACT_GELU ? 2 : in_act ? 3 : 0;
@@ -1427,10 +1423,9 @@ int wgrad_impl(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, co
   if (xf == 0) RDST_WG_LAUNCH(0) else if (xf == 1) RDST_WG_LAUNCH(1) else if (xf == 2) RDST_WG_LAUNCH(2) else if (xf == 4) RDST_WG_LAUNCH(4) else RDST_WG_LAUNCH(3)
 #undef RDST_WG_LAUNCH
   if (rc) return rc;
-  const int tot = N * p.Kx;
   if (lnfin) {
     rbatch::SumJob sj{};
-    sj.slab = slab; sj.nwg = (int)nwg; sj.stride = tot; sj.tot = tot; sj.map = rbatch::MAP_COPY; sj.out = G;
+    sj.slab = slab.p; sj.nwg = (int)nwg; sj.stride = tot; sj.tot = tot; sj.map = rbatch::MAP_COPY; sj.out = G;
     if (int rc = rbatch::sum(sj, st)) return rc;
     rbatch::FinJob fj{};
     fj.G = G; fj.Wt = Wt_fin; fj.gamma = ln_w; fj.beta = ln_b; fj.N = N; fj.K = K; fj.Kx = p.Kx; fj.s = s;
@@ -1438,7 +1433,7 @@ int wgrad_impl(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, co
     return rbatch::finish(fj, st);
   }
   rbatch::SumJob sj{};
-  sj.slab = slab; sj.nwg = (int)nwg; sj.stride = tot; sj.tot = tot; sj.map = rbatch::MAP_LINEAR;
+  sj.slab = slab.p; sj.nwg = (int)nwg; sj.stride = tot; sj.tot = tot; sj.map = rbatch::MAP_LINEAR;
   sj.out = dW; sj.out2 = dbias; sj.a = K; sj.b = p.Kx; sj.s = s;
   return rbatch::sum(sj, st);
 }
@@ -1446,7 +1441,7 @@ int wgrad_impl(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, co
 
 template <typename T>
 int linear_wgrad_mfma(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, const float* stats, int in_act,
-                      const T* dY, int64_t lddy, float* dW, float* dbias, float* slab, int64_t M, int K, int N, float s,
+                      const T* dY, int64_t lddy, float* dW, float* dbias, const WsSlab& slab, int64_t M, int K, int N, float s,
                       bool split, hipStream_t st) {
   return wgrad_impl<T>(X, ldx, ln_w, ln_b, stats, in_act, dY, lddy, dW, dbias, slab, M, K, N, s, nullptr, nullptr, nullptr,
                        nullptr, split, st);
@@ -1455,7 +1450,7 @@ int linear_wgrad_mfma(const T* X, int64_t ldx, const float* ln_w, const float* l
 // LayerNorm-fused Linear: dW, dbias AND d(gamma), d(beta) from one pass over (x-hat, dY).  G: N*(K+1) floats of scratch.
 template <typename T>
 int linear_wgrad_ln_mfma(const T* X, int64_t ldx, const float* ln_w, const float* ln_b, const float* stats, const float* Wt,
-                         const T* dY, int64_t lddy, float* dW, float* dbias, float* dln_w, float* dln_b, float* slab,
+                         const T* dY, int64_t lddy, float* dW, float* dbias, float* dln_w, float* dln_b, const WsSlab& slab,
                          float* G, int64_t M, int K, int N, float s, bool split, hipStream_t st) {
   if (!ln_w || !ln_b || !stats || !Wt || !G) return RDST_ENOTSUP;
   return wgrad_impl<T>(X, ldx, ln_w, ln_b, stats, 0, dY, lddy, dW, dbias, slab, M, K, N, s, Wt, G, dln_w, dln_b, split, st);
@@ -1482,7 +1477,7 @@ int linear_dgrad_ln2_mfma(const T* X, int64_t ldx, const float* stats, const flo
   if (smem > 160 * 1024) return RDST_ENOTSUP;
   const int64_t nslabs = (M + 31) / 32;
   int64_t grid = (nslabs + 7) / 8;
-  if (grid > 256) grid = 256;   // persistent, one workgroup per CU
+  if (grid > kCUs) grid = kCUs;   // persistent, one workgroup per CU
   int rc = 0;
 #define RDST_LND2_LAUNCH(NC)                                                                                          \
   {                                                                                                                  \
@@ -1498,16 +1493,16 @@ int linear_dgrad_ln2_mfma(const T* X, int64_t ldx, const float* stats, const flo
 
 #define INST(T)                                                                                                        \
   template int linear_dgrad_ln_mfma<T>(const T*, int64_t, const float*, const float*, const float*, const T*, int64_t, \
-                                       T*, int64_t, const T*, int64_t, float*, int*, int64_t, int, int, float,         \
+                                       T*, int64_t, const T*, int64_t, const WsSlab&, int*, int64_t, int, int, float,  \
                                        hipStream_t);                                                                   \
   template int linear_fwd_mfma<T>(const T*, int64_t, const float*, const float*, int, const float*, const float*,     \
                                   const T*, int64_t, T*, int64_t, float*, int64_t, int, int, float, bool, hipStream_t); \
   template int linear_dgrad_mfma<T>(const T*, int64_t, bool, int, const float*, const T*, int64_t, T*, int64_t,       \
                                     const T*, int64_t, float*, int64_t, int, int, float, bool, hipStream_t);          \
   template int linear_wgrad_mfma<T>(const T*, int64_t, const float*, const float*, const float*, int, const T*,       \
-                                    int64_t, float*, float*, float*, int64_t, int, int, float, bool, hipStream_t);   \
+                                    int64_t, float*, float*, const WsSlab&, int64_t, int, int, float, bool, hipStream_t); \
   template int linear_wgrad_ln_mfma<T>(const T*, int64_t, const float*, const float*, const float*, const float*,     \
-                                       const T*, int64_t, float*, float*, float*, float*, float*, float*, int64_t,    \
+                                       const T*, int64_t, float*, float*, float*, float*, const WsSlab&, float*, int64_t, \
                                        int, int, float, bool, hipStream_t);                                           \
   template int linear_dgrad_ln2_mfma<T>(const T*, int64_t, const float*, const float*, const float*, const T*, int64_t, \
                                         T*, int64_t, const T*, int64_t, int64_t, int, int, float, bool, hipStream_t);

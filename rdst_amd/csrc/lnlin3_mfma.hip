@@ -424,16 +424,15 @@ __global__ void __launch_bounds__((LB3<K, N>::NT), (LB3<K, N>::WPS)) lnlin3_bwd_
 }
 
 template <int K, int N, bool LN>
-int lb3_launch(LB3Args& p, int64_t max_wgs, int* grid_out, hipStream_t st) {
+int lb3_launch(LB3Args& p, const WsSlab& slab, int* grid_out, hipStream_t st) {
   using CF = LB3<K, N>;
   auto kern = lnlin3_bwd_kernel<K, N, LN>;
   static int percu_env = -1;
   if (percu_env < 0) { const char* e = rdst_dbg_getenv("RDST_LB3_PERCU"); percu_env = e ? atoi(e) : 0; }
   int per_cu = CF::PERCU;
   if (percu_env > 0 && percu_env < per_cu) per_cu = percu_env;
-  int64_t cap = 256 * (int64_t)per_cu;
-  if (cap > max_wgs) cap = max_wgs;
-  const int64_t grid = rdst_tile_grid(p.ntiles, cap, &p.tiles_per_wg);
+  const int64_t grid = rdst_tile_grid(p.ntiles, slab.cap((int64_t)kCUs * per_cu, 2 * p.slab_stride), &p.tiles_per_wg);   // (8-byte groups: 2 floats)
+  if (int rc = rdst_slab_fits(slab, grid, 2 * p.slab_stride, "lnlin3_bwd")) return rc;
   *grid_out = (int)grid;
   return rdst_launch(kern, dim3((unsigned)grid), dim3(CF::NT), CF::SMEM, st, "lnlin3_bwd", p);
 }
@@ -444,16 +443,16 @@ int lb3_launch(LB3Args& p, int64_t max_wgs, int* grid_out, hipStream_t st) {
 // lnlin_bwd_kernel).  Leaves one slab row per workgroup (*grid_out of them); the caller queues the reductions.
 int lnlin3_bwd_bf16(const bf16* X, int64_t ldx, const float* ln_w, const float* stats, const float* Wt, const bf16* dY,
                     int64_t lddy, bf16* dX, int64_t lddx, const bf16* acc, int64_t ldacc, const bf16* acc2, int64_t ldacc2,
-                    float* slab, int64_t slab_stride, int64_t M, int K, int N, int64_t max_wgs, int* grid_out, hipStream_t st) {
+                    const WsSlab& slab, int64_t slab_stride, int64_t M, int K, int N, int* grid_out, hipStream_t st) {
   static int off = -1;
   if (off < 0) { const char* e = rdst_dbg_getenv("RDST_LB3_OFF"); off = e ? atoi(e) : 0; }
   if (off) return RDST_ENOTSUP;
   const bool ln = ln_w != nullptr;
   LB3Args p{};
   p.X = X; p.ldx = ldx; p.stats = stats; p.lnw = ln_w; p.W = Wt; p.dY = dY; p.lddy = lddy; p.dX = dX; p.lddx = lddx;
-  p.Acc = acc; p.ldacc = ldacc; p.Acc2 = acc2; p.ldacc2 = ldacc2; p.slab = slab; p.slab_stride = slab_stride; p.M = M;
+  p.Acc = acc; p.ldacc = ldacc; p.Acc2 = acc2; p.ldacc2 = ldacc2; p.slab = slab.p; p.slab_stride = slab_stride; p.M = M;
   p.ntiles = (M + 31) / 32;
-#define RDST_LB3(KK, NN, LL) if (K == KK && N == NN && ln == LL) return lb3_launch<KK, NN, LL>(p, max_wgs, grid_out, st);
+#define RDST_LB3(KK, NN, LL) if (K == KK && N == NN && ln == LL) return lb3_launch<KK, NN, LL>(p, slab, grid_out, st);
   RDST_LB3(60, 180, true) RDST_LB3(90, 270, true) RDST_LB3(120, 360, true)
   RDST_LB3(60, 30, true) RDST_LB3(90, 30, true) RDST_LB3(120, 30, true)
   RDST_LB3(60, 60, false) RDST_LB3(90, 90, false) RDST_LB3(120, 120, false)

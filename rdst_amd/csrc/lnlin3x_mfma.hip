@@ -596,21 +596,20 @@ __global__ void __launch_bounds__((CF::NT), (CF::WPS)) lnlin3x_bwd_kernel(const 
 }
 
 template <int K, int N, int MODE, int DT, int TN, int TC>
-int lbx_launch(LBXArgs& p, int64_t max_wgs, int* grid_out, hipStream_t st) {
+int lbx_launch(LBXArgs& p, const WsSlab& slab, int* grid_out, hipStream_t st) {
   using CF = LBX<K, N, MODE, DT, TN, TC>;
   auto kern = lnlin3x_bwd_kernel<CF>;
   int per_cu = CF::NWV <= 6 && 2 * CF::SMEM <= 160 * 1024 ? 2 : 1;
-  int64_t cap = 256 * (int64_t)per_cu;
-  if (cap > max_wgs) cap = max_wgs;
-  const int64_t grid = rdst_tile_grid(p.ntiles, cap, &p.tiles_per_wg);
   p.slab_stride = (int64_t)N * (K + 1);
+  const int64_t grid = rdst_tile_grid(p.ntiles, slab.cap((int64_t)kCUs * per_cu, p.slab_stride), &p.tiles_per_wg);
+  if (int rc = rdst_slab_fits(slab, grid, p.slab_stride, "lnlin3x_bwd")) return rc;
   *grid_out = (int)grid;
   return rdst_launch(kern, dim3((unsigned)grid), dim3(CF::NT), CF::SMEM, st, "lnlin3x_bwd", p);
 }
 
 // one launch over output features [n0, n0 + NN) of a Linear with N outputs in all (NN = N: the whole layer)
-int lbx_dispatch(LBXArgs& p, int K, int NN, int mode, int64_t max_wgs, int* grid_out, hipStream_t st) {
-#define RDST_LBX(KK, NV, MM, DT, TN, TC) if (K == KK && NN == NV && mode == MM) return lbx_launch<KK, NV, MM, DT, TN, TC>(p, max_wgs, grid_out, st);
+int lbx_dispatch(LBXArgs& p, int K, int NN, int mode, const WsSlab& slab, int* grid_out, hipStream_t st) {
+#define RDST_LBX(KK, NV, MM, DT, TN, TC) if (K == KK && NN == NV && mode == MM) return lbx_launch<KK, NV, MM, DT, TN, TC>(p, slab, grid_out, st);
   // norm1 + qkv (C = 120: halves of 180 output features), proj, dense tails, norm2 + fc1, fc2 (GELU on the way in, K = 2 C)
   RDST_LBX(60, 180, BX_LN, 1, 3, 1) RDST_LBX(90, 270, BX_LN, 1, 3, 3) RDST_LBX(120, 180, BX_LN, 1, 3, 2)
   RDST_LBX(60, 60, BX_PLAIN, 1, 1, 2) RDST_LBX(90, 90, BX_PLAIN, 1, 1, 3) RDST_LBX(120, 120, BX_PLAIN, 1, 2, 2)
@@ -638,7 +637,7 @@ int lnlin3x_bwd_kind(int K, int N, bool ln, int in_act) {
 // falls back to the three-launch path of linear_mfma.hip).  Queues / runs the slab sums and the LayerNorm finish itself.
 int lnlin3x_bwd_f32(const float* X, int64_t ldx, const float* ln_w, const float* ln_b, const float* stats, int in_act, const float* Wt,
                     const float* dY, int64_t lddy, float* dX, int64_t lddx, const float* acc, int64_t ldacc, const float* acc2,
-                    int64_t ldacc2, float* dW, float* dbias, float* dln_w, float* dln_b, float* slab, float* G, int64_t M, int K, int N,
+                    int64_t ldacc2, float* dW, float* dbias, float* dln_w, float* dln_b, const WsSlab& slab, float* G, int64_t M, int K, int N,
                     float s, hipStream_t st) {
   const bool ln = ln_w != nullptr;
   const int kind = lnlin3x_bwd_kind(K, N, ln, in_act);
@@ -647,20 +646,19 @@ int lnlin3x_bwd_f32(const float* X, int64_t ldx, const float* ln_w, const float*
   const int mode = ln ? BX_LN : in_act == RDST_ACT_GELU ? BX_GELU : BX_PLAIN;
   if (mode == BX_GELU && (acc || acc2)) return RDST_ENOTSUP;
   if (((M - 1) * ldx + K) * 4 >= (1ll << 31) || ((M - 1) * lddy + N) * 4 >= (1ll << 31) || M * 8 >= (1ll << 31)) return RDST_ENOTSUP;   // 32-bit DMA offsets
-  const int max_wgs = linear_wgrad_max_wgs(N);
   const int NN = kind == 2 ? N / 2 : N;
   for (int half = 0; half < kind; ++half) {
     const int n0 = half * NN;
     LBXArgs p{};
     p.X = X; p.ldx = ldx; p.stats = stats; p.lnw = ln_w; p.W = Wt + (int64_t)n0 * K; p.dY = dY + n0; p.lddy = lddy; p.dX = dX; p.lddx = lddx;
     p.Acc = half == 0 ? acc : dX; p.ldacc = half == 0 ? ldacc : lddx; p.Acc2 = half == 0 ? acc2 : nullptr; p.ldacc2 = ldacc2;
-    float* sl = slab + (int64_t)half * max_wgs * NN * (K + 1);   // (the region holds max_wgs slabs of N x (K + 1): half the rows each)
-    p.slab = sl; p.M = M; p.ntiles = (M + 31) / 32;
+    const WsSlab sl = slab.part(half, kind);   // (the region's rows of N x (K + 1), as `kind` blocks of rows of NN x (K + 1))
+    p.slab = sl.p; p.M = M; p.ntiles = (M + 31) / 32;
     p.x_bytes = (int)(((M - 1) * ldx + K) * 4); p.y_bytes = (int)(((M - 1) * lddy + NN) * 4);
     int grid = 0;
-    if (int rc = lbx_dispatch(p, K, NN, mode, max_wgs, &grid, st)) return rc;
+    if (int rc = lbx_dispatch(p, K, NN, mode, sl, &grid, st)) return rc;
     rbatch::SumJob sj{};
-    sj.slab = sl; sj.nwg = grid; sj.stride = (int64_t)NN * (K + 1); sj.g4 = 0; sj.tot = NN * (K + 1);
+    sj.slab = sl.p; sj.nwg = grid; sj.stride = (int64_t)NN * (K + 1); sj.g4 = 0; sj.tot = NN * (K + 1);
     if (!ln) {
       sj.map = rbatch::MAP_LINEAR; sj.out = dW; sj.out2 = dbias; sj.a = K; sj.b = K + 1; sj.s = 1.0f;
     } else {

@@ -374,7 +374,7 @@ static int lnlin_bwd_reduce(float* slab, int grid, int64_t slab_stride, bool ln,
 // N <= 384, out_scale 1, no input activation; RDST_ENOTSUP otherwise
 int linear_ln_bwd_fused_bf16(const bf16* X, int64_t ldx, const float* ln_w, const float* ln_b, const float* stats,
                              const float* Wt, const bf16* dY, int64_t lddy, bf16* dX, int64_t lddx, const bf16* acc,
-                             int64_t ldacc, float* dW, float* dbias, float* dln_w, float* dln_b, float* slab, float* G,
+                             int64_t ldacc, float* dW, float* dbias, float* dln_w, float* dln_b, const WsSlab& slab, float* G,
                              int64_t M, int K, int N, float s, hipStream_t st, const bf16* acc2, int64_t ldacc2) {
   static int off = -1;
   if (off < 0) { const char* e = rdst_dbg_getenv("RDST_LNLIN_V1"); off = e ? atoi(e) : 0; }   // 1: all off, 2: the plain-Linear form off
@@ -400,8 +400,8 @@ int linear_ln_bwd_fused_bf16(const bf16* X, int64_t ldx, const float* ln_w, cons
     int g3 = 0;
     if (acc2 && (((uintptr_t)acc2 & 3) || (ldacc2 & 1) || (uint64_t)M * (uint64_t)ldacc2 * 2 >= (1ull << 31))) return RDST_ENOTSUP;
     const int rc3 = lnlin3_bwd_bf16(X, ldx, ln_w, stats, Wt, dY, lddy, dX, lddx, acc, ldacc, acc2, ldacc2, slab, slab_stride, M, K,
-                                    N, linear_wgrad_max_wgs(N), &g3, st);
-    if (rc3 == 0) return lnlin_bwd_reduce(slab, g3, slab_stride, ln, Wt, ln_w, ln_b, dW, dbias, dln_w, dln_b, G, N, K, st);
+                                    N, &g3, st);
+    if (rc3 == 0) return lnlin_bwd_reduce(slab.p, g3, slab_stride, ln, Wt, ln_w, ln_b, dW, dbias, dln_w, dln_b, G, N, K, st);
     if (rc3 != RDST_ENOTSUP || acc2) return rc3;   // (only the re-cut kernel takes a second addend)
   }
   const int CP = 32 * nct, LDW = nct == 4 ? 288 : CP * 2 + 16, LDX = nct == 4 ? 336 : CP * 2 + 16, NP = 32 * NW, LDY = lnlin_ldy(NP);
@@ -417,11 +417,10 @@ int linear_ln_bwd_fused_bf16(const bf16* X, int64_t ldx, const float* ln_w, cons
   if (per_cu < 1) per_cu = 1;
   if (per_cu > 2) per_cu = 2;   // more workgroups only add slab traffic (measured)
   { const char* e = rdst_dbg_getenv("RDST_LNLIN_PERCU"); if (e && atoi(e) > 0) per_cu = atoi(e); }
-  int64_t cap = 256 * per_cu;
-  if (cap > linear_wgrad_max_wgs(N)) cap = linear_wgrad_max_wgs(N);   // what the workspace's slab region holds
-  const int64_t grid = rdst_tile_grid(p.ntiles, cap, &p.tiles_per_wg);
-  p.slab = slab;
-  p.slab_stride = (int64_t)((N + 3) / 4) * (K + 1);   // bf16 G4 slab: 8-byte groups
+  p.slab = slab.p;
+  p.slab_stride = slab_stride;
+  const int64_t grid = rdst_tile_grid(p.ntiles, slab.cap((int64_t)kCUs * per_cu, 2 * slab_stride), &p.tiles_per_wg);   // (8-byte groups: 2 floats)
+  if (int rc = rdst_slab_fits(slab, grid, 2 * slab_stride, "lnlin_bwd")) return rc;
   int rc = 0;
 #define RDST_LNLIN(NC)                                                                                               \
   {                                                                                                                  \
@@ -433,5 +432,5 @@ int linear_ln_bwd_fused_bf16(const bf16* X, int64_t ldx, const float* ln_w, cons
 #undef RDST_LNLIN
   rdst_stamps_end(p.stamps, grid, 16, RDST_STAMPS_TICKS, st, "lnlin_bwd K=%d N=%d ln=%d", K, N, (int)ln);
   if (rc) return rc;
-  return lnlin_bwd_reduce(slab, (int)grid, p.slab_stride, ln, Wt, ln_w, ln_b, dW, dbias, dln_w, dln_b, G, N, K, st);
+  return lnlin_bwd_reduce(slab.p, (int)grid, p.slab_stride, ln, Wt, ln_w, ln_b, dW, dbias, dln_w, dln_b, G, N, K, st);
 }

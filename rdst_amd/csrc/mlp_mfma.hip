@@ -894,11 +894,27 @@ extern "C" int rdst_mlp_fused_supported(int C, int hid, int dtype) {
   return dtype == RDST_BF16 && mlp_fused(C, hid);
 }
 
+// ---- the backward workspace: [slab][G] ---------------------------------------------------------------------------------------------
+namespace {
+struct MlpBwdWs {
+  WsSlab slab;   // mlp_bwd per workgroup: fp32-sized rows [hid][C+1] | [hid+1][C], written as bf16 G4 groups (half the floats)
+  float* G;      // [hid][C+1]: the summed region 1, for the LayerNorm finish (wgrad_ln_finish)
+  size_t bytes;
+};
+MlpBwdWs mlp_bwd_layout(void* base, int C, int hid) {
+  WsCarver c(base);
+  MlpBwdWs w{};
+  w.slab = ws_take_slab(c, 2 * kCUs, (int64_t)hid * (C + 1) + (int64_t)(hid + 1) * C);   // two workgroups per CU at the narrow widths
+  w.G = c.take<float>((size_t)hid * (C + 1) + kWsSlackFloats);
+  w.bytes = c.bytes();
+  return w;
+}
+}  // namespace
+
 extern "C" size_t rdst_mlp_bwd_workspace(int64_t M, int C, int hid) {
   (void)M;
   if (C <= 0 || hid <= 0) return 0;
-  const size_t per = (size_t)hid * (C + 1) + (size_t)(hid + 1) * C;
-  return sizeof(float) * (512 * per + (size_t)hid * (C + 1) + 64);
+  return mlp_bwd_layout(nullptr, C, hid).bytes;
 }
 
 extern "C" int rdst_mlp_bwd(const void* X, int64_t ld_x, const float* ln_w, const float* ln_b, const float* stats,
@@ -922,13 +938,15 @@ extern "C" int rdst_mlp_bwd(const void* X, int64_t ld_x, const float* ln_w, cons
   p.ntiles = (M + 31) / 32;
   // narrow layers (4 waves, <= 256 registers in total per SIMD lane pair, 37 KB of LDS) run TWO workgroups per CU: one
   // wave per SIMD hides no latency, and two independent workgroups overlap each other's phases
-  int64_t cap = nct == 2 ? 512 : 256;
+  int64_t cap = nct == 2 ? 2 * kCUs : kCUs;
   { const char* e = rdst_dbg_getenv("RDST_MLP_GRID"); if (e && atoi(e) > 0) cap = atoi(e); }
-  const int64_t grid = rdst_tile_grid(p.ntiles, cap, &p.tiles_per_wg);
-  p.slab = (float*)workspace;
+  const MlpBwdWs w = mlp_bwd_layout(workspace, C, hid);
+  p.slab = w.slab.p;
   // bf16 G4 slabs: (hid/4) x (C+1) groups of region 1 + (hid/4 + 1) x C groups of region 2, 8 bytes each (2 floats)
   p.slab_stride = (int64_t)((hid + 3) / 4) * (C + 1) + (int64_t)((hid + 4) / 4) * C;
-  float* G = p.slab + 512 * ((int64_t)hid * (C + 1) + (int64_t)(hid + 1) * C);   // (behind the fp32-sized slab region)
+  const int64_t grid = rdst_tile_grid(p.ntiles, w.slab.cap(cap, 2 * p.slab_stride), &p.tiles_per_wg);
+  if (int rc = rdst_slab_fits(w.slab, grid, 2 * p.slab_stride, "mlp_bwd")) return rc;
+  float* const G = w.G;
   int rc = 0;
 #define RDST_MLPB(NC)                                                                                                \
   {                                                                                                                  \
@@ -988,7 +1006,7 @@ extern "C" int rdst_mlp_fwd(const void* X, int64_t ld_x, const float* ln_w, cons
   p.X = (const bf16*)X; p.ldx = ld_x; p.lnw = ln_w; p.lnb = ln_b; p.W1 = W1; p.b1 = b1; p.W2 = W2; p.b2 = b2;
   p.Y = (bf16*)Y; p.ldy = ld_y; p.stats = stats; p.M = M; p.C = C; p.hid = hid;
   p.ntiles = (M + 31) / 32;
-  int64_t cap = nct == 2 ? 512 : 256;   // the narrow layers fit two workgroups per CU (see rdst_mlp_bwd)
+  int64_t cap = nct == 2 ? 2 * kCUs : kCUs;   // the narrow layers fit two workgroups per CU (see rdst_mlp_bwd)
   { const char* e = rdst_dbg_getenv("RDST_MLP_GRID"); if (e && atoi(e) > 0) cap = atoi(e); }
   const int64_t grid = rdst_tile_grid(p.ntiles, cap, &p.tiles_per_wg);
   int rc = 0;

@@ -77,7 +77,7 @@ static inline int wattn_gran(int sec_bytes, std::initializer_list<const void*> p
 }
 // window groups of the persistent K2 kernels (one slab row each): one per CU, per window and per slab row at most
 static inline int64_t k2_groups(int64_t nwin, int slab_rows) {
-  int64_t G = 256;
+  int64_t G = kCUs;
   if (G > nwin) G = nwin;
   if (G > slab_rows) G = slab_rows;
   return G;

@@ -9,12 +9,17 @@ thread_local char g_rdst_err[256] = {0};
 extern "C" int rdst_abi_version(void) { return 11; }
 extern "C" const char* rdst_last_error(void) { return g_rdst_err; }
 
+// The backward workspace of rdst_wattn_bwd / _bwd_lse / _bwd_drop is one region: a partial d(table) [heads][T] per slab row, one
+// row per window.  The kernels that write a row per window refuse fewer rows; the persistent ones cap their grid by them (k2_groups).
+static WsSlab wattn_bwd_layout(void* base, int B, int H, int W, int heads, int ws) {
+  WsCarver c(base);
+  return ws_take_slab(c, (int64_t)B * (H / ws) * (W / ws), (int64_t)heads * (2 * ws - 1) * (2 * ws - 1));
+}
 extern "C" size_t rdst_wattn_bwd_workspace(int B, int H, int W, int C, int heads, int ws) {
   if (B <= 0 || H <= 0 || W <= 0 || ws <= 0 || heads <= 0) return 0;
-  const size_t nwin = (size_t)B * (H / ws) * (W / ws);
-  const size_t T = (size_t)(2 * ws - 1) * (2 * ws - 1);
   (void)C;
-  return nwin * heads * T * sizeof(float);
+  const WsSlab s = wattn_bwd_layout(nullptr, B, H, W, heads, ws);
+  return (size_t)s.rows * s.stride * sizeof(float);
 }
 
 namespace {
@@ -161,12 +166,12 @@ extern "C" int rdst_wattn_bwd(const void* qkv, int64_t ld_qkv, const float* tabl
                                 {qkv, table, dout, dqkv, dtable, workspace}, {ld_qkv, ld_dqkv}, {ld_dout}, workspace_bytes))
     return rc;
   hipStream_t st = (hipStream_t)stream;
-  float* slab = (float*)workspace;
+  const WsSlab slab = wattn_bwd_layout(workspace, B, H, W, heads, ws);
   int nslab = 0;   // slab rows written: one per persistent workgroup, or one per window
-  if (int rc = wattn_route(kBwdRoutes, BwdCall{qkv, ld_qkv, table, dout, ld_dout, dqkv, ld_dqkv, slab, B * g.nWh * g.nWw, g, scale,
+  if (int rc = wattn_route(kBwdRoutes, BwdCall{qkv, ld_qkv, table, dout, ld_dout, dqkv, ld_dqkv, slab.p, (int)slab.rows, g, scale,
                                                dtype, split, &nslab, st}))
     return rc;
-  return wattn_sum_dtable(slab, nslab, heads, g.T, dtable, st);
+  return wattn_sum_dtable(slab.p, nslab, heads, g.T, dtable, st);
 }
 
 // ---- K8: the attention half of a Swin block in one launch (swinattn_fwd.hip) ---------------------------------------------------
@@ -217,12 +222,12 @@ extern "C" int rdst_wattn_bwd_lse(const void* qkv, int64_t ld_qkv, const float* 
     return rc;
   if (dtype != RDST_BF16) return RDST_ENOTSUP;
   hipStream_t st = (hipStream_t)stream;
-  float* slab = (float*)workspace;
+  const WsSlab slab = wattn_bwd_layout(workspace, B, H, W, heads, ws);
   int nslab = 0;
-  if (int rc = wattn16_bwd_mfma(qkv, ld_qkv, table, dout, ld_dout, dqkv, ld_dqkv, slab, B * g.nWh * g.nWw, g, scale, &nslab, st, out,
+  if (int rc = wattn16_bwd_mfma(qkv, ld_qkv, table, dout, ld_dout, dqkv, ld_dqkv, slab.p, (int)slab.rows, g, scale, &nslab, st, out,
                                 ld_out, nlse))
     return rc;
-  return wattn_sum_dtable(slab, nslab, heads, g.T, dtable, st);
+  return wattn_sum_dtable(slab.p, nslab, heads, g.T, dtable, st);
 }
 
 // ---- attention dropout (WindowAttention.attn_drop > 0 in training, swin_transformer_sr.py:102,136): the generic kernels with
@@ -261,9 +266,9 @@ extern "C" int rdst_wattn_bwd_drop(const void* qkv, int64_t ld_qkv, const float*
     return rc;
   if (int rc = drop_args(g, attn_drop, seed, "rdst_wattn_bwd_drop")) return rc;
   hipStream_t st = (hipStream_t)stream;
-  float* slab = (float*)workspace;
-  if (int rc = wattn_bwd_generic(qkv, ld_qkv, table, dout, ld_dout, dqkv, ld_dqkv, slab, g, scale, dtype, st)) return rc;
-  return wattn_sum_dtable(slab, B * g.nWh * g.nWw, heads, g.T, dtable, st);   // one slab row per (window, head) workgroup: [nwin][heads][T]
+  const WsSlab slab = wattn_bwd_layout(workspace, B, H, W, heads, ws);
+  if (int rc = wattn_bwd_generic(qkv, ld_qkv, table, dout, ld_dout, dqkv, ld_dqkv, slab.p, g, scale, dtype, st)) return rc;
+  return wattn_sum_dtable(slab.p, (int)slab.rows, heads, g.T, dtable, st);   // one slab row per (window, head) workgroup: [nwin][heads][T]
 }
 
 // The multipliers (0 or 1 / (1 - attn_drop)) the two entry points above apply: out[(window * heads + head)][N][N] floats

@@ -377,7 +377,7 @@ int launch_fwd(const T* qkv, int64_t ld, const float* table, T* out, int64_t ldo
   int wg_per_cu = (int)((160 * 1024) / smem);
   if (wg_per_cu > 4) wg_per_cu = 4;
   if (wg_per_cu < 1) wg_per_cu = 1;
-  int64_t grid = 256 * wg_per_cu;
+  int64_t grid = (int64_t)kCUs * wg_per_cu;
   if (grid > nwin) grid = nwin;
   int rc = 0;
 #define RDST_WA_LAUNCH1(GR, KM, NWV)                                                                                  \

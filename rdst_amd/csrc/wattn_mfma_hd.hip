@@ -426,7 +426,7 @@ int launch_hd(const HdArgs& p, hipStream_t st) {
     }
     if (env_wgs > 0 && env_wgs < wg_per_cu) wg_per_cu = env_wgs;
   }
-  int64_t grid = 256 * (int64_t)wg_per_cu;
+  int64_t grid = (int64_t)kCUs * wg_per_cu;
   if (grid > nwin) grid = nwin;
   HdArgs q = p;   // (debug: in-kernel stamps of every workgroup, relative to its own start: the clocks differ per XCD)
   q.stamps = rdst_stamps_begin("RDST_K1_STAMPS", grid, 16, st);

@@ -25,6 +25,9 @@ WIDTHS = (0, 1, 8, 30, 48, 59, 60, 61, 64, 90, 96, 120, 150, 180, 240, 270, 360)
 HEADS = (1, 3, 6, 8)
 WINDOWS = (4, 8, 16)
 ACTS = (_lib.ACT_NONE, _lib.ACT_GELU, _lib.ACT_LEAKY02)
+# the backward workspaces: token counts around the 32-row tile and at step size, pixel grids of one and of several tiles
+TOKENS = (1, 31, 32, 33, 4096, 65536)
+IMAGES = ((1, 8, 8), (1, 40, 32), (2, 64, 64))
 
 
 def grids():
@@ -40,6 +43,10 @@ def grids():
         "rdst_swin_attn_fwd_supported": [(c, h, ws, dt) for c in WIDTHS for h in HEADS for ws in WINDOWS for dt in DTYPES],
         "rdst_conv_fwd_workspace2": [(ci, co, ks, dt) for ci, co in w2 for ks in (1, 3) for dt in DTYPES],
         "rdst_ln_linear_fwd_workspace2": [(k, n, dt) for k, n in w2 for dt in DTYPES],
+        "rdst_ln_linear_bwd_workspace": [(m, k, n) for m in TOKENS for k, n in w2],
+        "rdst_mlp_bwd_workspace": [(m, c, h) for m in TOKENS for c, h in w2],
+        "rdst_conv_bwd_workspace": [(b, h, w, ci, co, ks) for b, h, w in IMAGES for ci, co in w2 for ks in (1, 3)],
+        "rdst_wattn_bwd_workspace": [(b, h, w, c, hd, ws) for b, h, w in IMAGES for c in WIDTHS for hd in HEADS for ws in WINDOWS],
     }
 
 

@@ -3,7 +3,10 @@
 shapes that decide the choice: window attention forward and backward (ws 4 / 8 / 16, heads 6 / 3, C 48 / 60 / 90 / 120, dense
 rows, strided rows, a base pointer off by 4 bytes, an explicit mask, bf16 / fp32 / fp32x3; 2 to 4 windows, so fewer slab rows
 than the 256 of a full grid), the fused Mlp forward (with and without the packed-weight workspace) and backward at C 48 / 60 /
-120, and the bf16 Linear backward at (60, 180), (120, 30), (48, 48) with and without LayerNorm.
+120, the bf16 Linear backward at (60, 180), (120, 30), (48, 48) with and without LayerNorm, the fp32 / fp32x3 Linear backward
+at (60, 180) and (120, 360) behind a LayerNorm (the latter in two half launches) and (60, 60) plain, at 64 and 4096 tokens, and
+the conv backward in the three modes at 1 x 32 x 32: the three register-stationary shapes, a generic 100 -> 130 conv and the
+one-channel tail and head convs.
 
     rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/launch_trace.py run     # one line per call on stdout
     python tools/launch_trace.py summarize DIR/**/*_kernel_trace.csv > LIST                     # name, grid, workgroup, LDS
@@ -96,10 +99,11 @@ def mlp(torch, lib, C, packed, M=160):
     return rf, rb, dict(zip(("y", "stats", "dx", "dW1", "db1", "dW2", "db2", "dg", "dbeta"), [y, stats, dx, *g]))
 
 
-def linear_bwd(torch, lib, K, N, ln, M=160):
-    """bf16 Linear backward (one pass where the shape allows): -> (rc, tensors)"""
-    x, px = _rows(torch, M, K, K, torch.bfloat16, 1)
-    gy, pg = _rows(torch, M, N, N, torch.bfloat16, 2)
+def linear_bwd(torch, lib, K, N, ln, M=160, dt="bf16"):
+    """Linear backward (one pass where the shape allows): -> (rc, tensors)"""
+    tdt = torch.bfloat16 if dt == "bf16" else torch.float32
+    x, px = _rows(torch, M, K, K, tdt, 1)
+    gy, pg = _rows(torch, M, N, N, tdt, 2)
     dx = torch.zeros_like(x)
     w = _par(torch, (N, K), 3, K ** -0.5)
     lw, lb = 1 + _par(torch, (K,), 4, 0.1), _par(torch, (K,), 5, 0.1)
@@ -111,10 +115,31 @@ def linear_bwd(torch, lib, K, N, ln, M=160):
     torch.cuda.synchronize()
     rc = lib.rdst_ln_linear_bwd(px, K, lw.data_ptr() if ln else None, lb.data_ptr() if ln else None, stats.data_ptr() if ln else None, 0,
                                 w.data_ptr(), pg, N, dx.data_ptr(), K, None, 0, dw.data_ptr(), db.data_ptr(),
-                                dlw.data_ptr() if ln else None, dlb.data_ptr() if ln else None, wsp.data_ptr(), nb, M, K, N, 1.0, 1,
+                                dlw.data_ptr() if ln else None, dlb.data_ptr() if ln else None, wsp.data_ptr(), nb, M, K, N, 1.0, DT[dt],
                                 torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     return rc, {"dx": dx, "dW": dw, "db": db, **({"dg": dlw, "dbeta": dlb} if ln else {})}
+
+
+CONVS = ((150, 60, 3, 1), (60, 60, 3, 1), (60, 240, 3, 2), (100, 130, 3, 1), (60, 1, 3, 1), (1, 60, 3, 1))   # Cin, Cout, ks, shuffle
+
+
+def conv_bwd(torch, lib, dt, Cin, Cout, ks, r, B=1, H=32, W=32):
+    """conv backward, every gradient (the head conv: no data gradient): -> (rc, tensors)"""
+    tdt = torch.bfloat16 if dt == "bf16" else torch.float32
+    n, cy = B * H * W, Cout // (r * r)
+    x, px = _rows(torch, n, Cin, Cin, tdt, 1)
+    gy, pg = _rows(torch, n * r * r, cy, cy, tdt, 2)
+    dx = torch.zeros_like(x)
+    w = _par(torch, (Cout, Cin, ks, ks), 3, (Cin * ks * ks) ** -0.5)
+    dw, db = torch.zeros_like(w), torch.zeros(Cout, device="cuda")
+    nb = lib.rdst_conv_bwd_workspace(B, H, W, Cin, Cout, ks)
+    wsp = torch.empty(nb, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    rc = lib.rdst_conv_bwd(px, Cin, 0, w.data_ptr(), pg, cy, dx.data_ptr() if Cin > 1 else None, Cin, None, 0, dw.data_ptr(), db.data_ptr(),
+                           wsp.data_ptr(), nb, B, H, W, Cin, Cout, ks, 1.0, r, DT[dt], torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return rc, {"dx": dx, "dW": dw, "db": db}
 
 
 def calls(torch, lib):
@@ -128,6 +153,12 @@ def calls(torch, lib):
     for (K, N), ln in itertools.product(((60, 180), (120, 30), (48, 48)), (True, False)):
         rc, t = linear_bwd(torch, lib, K, N, ln)
         yield "linear_bwd %d->%d%s" % (K, N, " ln" if ln else ""), (rc,), t
+    for dt, (K, N, ln), M in itertools.product(("fp32", "fp32x3"), ((60, 180, True), (120, 360, True), (60, 60, False)), (64, 4096)):
+        rc, t = linear_bwd(torch, lib, K, N, ln, M, dt)
+        yield "linear_bwd %s %d->%d%s M%d" % (dt, K, N, " ln" if ln else "", M), (rc,), t
+    for dt, c in itertools.product(DT, CONVS):
+        rc, t = conv_bwd(torch, lib, dt, *c)
+        yield "conv_bwd %s %d->%d k%d r%d" % (dt, *c), (rc,), t
 
 
 def summarize(paths):
