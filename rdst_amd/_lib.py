@@ -1,130 +1,112 @@
 """ctypes binding of librdst_hip.so (the C ABI of include/rdst_hip.h).  Fails loudly: there is no
-fallback when the library is missing."""
+fallback when the library is missing.
+
+The header is the table: its declarations, structs and integer ``#define``s are parsed once at import, so the binding of
+a new entry point is its declaration in include/rdst_hip.h and nothing else.  tests/test_abi_host.py pins what the parse
+yields against a recording of the hand-written table it replaced."""
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RDST_HIP_LIB: load another build of the same C ABI (tools/ use it for the -DRDST_DEBUG library); the default
 # is the in-tree release library, and a missing file raises either way
 LIB_PATH = os.environ.get("RDST_HIP_LIB") or os.path.join(_HERE, "librdst_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rdst_hip.h")
 
-F32, BF16, F32X3 = 0, 1, 2
-EINVAL, ENOTSUP = -10001, -10002
-ACT_NONE, ACT_GELU, ACT_LEAKY02, ACT_LEAKY001 = 0, 1, 2, 3
-
-_p, _i, _l, _f, _z = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
-
-
-class LrSchedule(C.Structure):   # rdst_lr_schedule, passed by value to rdst_adam_step_dev
-    MAX_MILESTONES = 16
-    _fields_ = [("milestones", C.c_int64 * 16), ("lr", C.c_float * 17), ("count", C.c_int32)]
+_SCALARS = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
+_FIELD_SCALARS = {**_SCALARS, "int32_t": C.c_int32}
+_RETURNS = {"int": C.c_int, "size_t": C.c_size_t, "const char*": C.c_char_p}
+_POINTEES = {*_FIELD_SCALARS, "void", "char", "uint8_t", "unsigned long long"}   # what a pointer may point to, besides the structs
 
 
-STEP_STATE_BYTES = 48            # rdst_step_state
-SKIP_LOSS, SKIP_NONFINITE, SKIP_PEER = 1, 2, 4
+def _ctype(text, scalars, structs, where):
+    """The ctypes class of one C type of the header; `structs` (by value, or pointed to) are the ones parsed so far."""
+    ty = re.sub(r"\s*\*", "*", " ".join(text.split()))
+    if ty == "int*":
+        return C.POINTER(C.c_int)    # the one typed pointer: rdst_u_conv's host-side block count
+    if ty.endswith("*") and ty[:-1].removeprefix("const ") in _POINTEES | set(structs):
+        return C.c_void_p
+    if ty in scalars or ty in structs:
+        return scalars.get(ty) or structs[ty]
+    raise RuntimeError(f"rdst_amd: include/rdst_hip.h: type '{ty}' is not in the binding's type map, in: {where}")
 
-# name -> (restype, argtypes); must list every symbol include/rdst_hip.h declares
-SIGNATURES = {
-    "rdst_abi_version": (_i, []),
-    "rdst_last_error": (C.c_char_p, []),
-    "rdst_wattn_fwd": (_i, [_p, _l, _p, _p, _i, _p, _l, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "rdst_wattn_bwd_workspace": (_z, [_i, _i, _i, _i, _i, _i]),
-    "rdst_wattn_bwd": (_i, [_p, _l, _p, _p, _i, _p, _l, _p, _l, _p, _p, _z, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "rdst_ln_linear_fwd_workspace": (_z, [_i, _i]),
-    "rdst_ln_linear_fwd_workspace2": (_z, [_i, _i, _i]),
-    "rdst_ln_linear_fwd": (_i, [_p, _l, _p, _p, _i, _p, _p, _p, _l, _p, _l, _p, _p, _z, _l, _i, _i, _f, _i, _p]),
-    "rdst_ln_linear_bwd_workspace": (_z, [_l, _i, _i]),
-    "rdst_ln_linear_bwd": (_i, [_p, _l, _p, _p, _p, _i, _p, _p, _l, _p, _l, _p, _l, _p, _p, _p, _p, _p, _z,
-                                _l, _i, _i, _f, _i, _p]),
-    "rdst_ln_linear_bwd2": (_i, [_p, _l, _p, _p, _p, _i, _p, _p, _l, _p, _l, _p, _l, _p, _p, _p, _p, _p, _z,
-                                 _l, _i, _i, _f, _i, _p, _p, _l]),
-    "rdst_mlp_fused_supported": (_i, [_i, _i, _i]),
-    "rdst_mlp_fwd_workspace": (_z, [_i, _i]),
-    "rdst_mlp_fwd_packable": (_i, [_i, _i, _i]),
-    "rdst_mlp_fwd": (_i, [_p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _z, _l, _i, _i, _i, _p]),
-    "rdst_mlp_bwd_workspace": (_z, [_l, _i, _i]),
-    "rdst_mlp_bwd": (_i, [_p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p, _p, _p, _p, _p, _p, _p, _z, _l, _i, _i, _i,
-                          _p]),
-    "rdst_wattn_fwd_lse": (_i, [_p, _l, _p, _p, _l, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "rdst_wattn_bwd_lse": (_i, [_p, _l, _p, _p, _l, _p, _l, _p, _p, _l, _p, _p, _z, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "rdst_swin_attn_fwd_supported": (_i, [_i, _i, _i, _i]),
-    "rdst_swin_attn_fwd_workspace": (_z, [_i]),
-    "rdst_swin_attn_fwd": (_i, [_p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p, _l, _p, _p, _z, _i, _i, _i, _i, _i, _i, _i,
-                                _f, _i, _p]),
-    "rdst_conv_fwd_workspace": (_z, [_i, _i, _i]),
-    "rdst_conv_fwd_workspace2": (_z, [_i, _i, _i, _i]),
-    "rdst_conv_fwd": (_i, [_p, _l, _i, _p, _p, _p, _l, _p, _l, _p, _z, _i, _i, _i, _i, _i, _i, _f, _i, _i, _p]),
-    "rdst_conv_bwd_workspace": (_z, [_i, _i, _i, _i, _i, _i]),
-    "rdst_conv_bwd": (_i, [_p, _l, _i, _p, _p, _l, _p, _l, _p, _l, _p, _p, _p, _z, _i, _i, _i, _i, _i, _i,
-                           _f, _i, _i, _p]),
-    "rdst_pack_batch": (_i, [_p, _i, _p]),
-    "rdst_ln_linear_fwd_packable": (_i, [_i, _i, _i, _i, _i, _i]),
-    "rdst_conv_fwd_packable": (_i, [_i, _i, _i, _i, _i, _i, _i]),
-    "rdst_reduce_batch_begin": (_i, []),
-    "rdst_reduce_batch_end": (_i, [_p]),
-    "rdst_reduce_batch_abort": (_i, []),
-    "rdst_side_enable": (_i, [_i]),
-    "rdst_side_join": (_i, [_p]),
-    "rdst_side_reset": (_i, []),
-    "rdst_wattn_fwd_drop": (_i, [_p, _l, _p, _p, _i, _p, _l, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _p, _p]),
-    "rdst_wattn_bwd_drop": (_i, [_p, _l, _p, _p, _i, _p, _l, _p, _l, _p, _p, _z, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _p, _p]),
-    "rdst_wattn_drop_mask": (_i, [_p, _i, _i, _i, _i, _i, _f, _p, _p]),
-    "rdst_nchw_to_rows": (_i, [_p, _p, _l, _i, _i, _i, _i, _i, _p]),
-    "rdst_rows_to_nchw": (_i, [_p, _l, _p, _i, _i, _i, _i, _i, _p]),
-    "rdst_upsample2_fwd": (_i, [_p, _l, _p, _l, _i, _i, _i, _i, _i, _p]),
-    "rdst_upsample2_bwd": (_i, [_p, _l, _p, _l, _i, _i, _i, _i, _i, _p]),
-    "rdst_adam_step": (_i, [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _l, _p]),
-    # the seg-UNet of the perceptual loss (ABI v5)
-    "rdst_u_scratch_bytes": (_z, []),
-    "rdst_u_conv": (_i, [_p, _l, _i, _i, _p, _l, _i, _p, _p, _p, _l, _p, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p,
-                         C.POINTER(C.c_int)]),
-    "rdst_u_bn_stats_from": (_i, [_p, _i, _l, _i, _p, _p, _f, _f, _p, _p, _p, _p, _p]),
-    "rdst_u_stem_fwd": (_i, [_p, _p, _p, _l, _i, _i, _i, _i, _i, _p]),
-    "rdst_u_stem_dgrad": (_i, [_p, _l, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
-    "rdst_u_bn_stats": (_i, [_p, _l, _l, _i, _p, _p, _f, _f, _p, _p, _p, _p, _i, _p]),
-    "rdst_u_bn_apply": (_i, [_p, _l, _p, _p, _l, _p, _p, _l, _i, _p, _l, _l, _i, _i, _p]),
-    "rdst_u_bn_bwd": (_i, [_p, _l, _p, _l, _p, _l, _p, _p, _l, _p, _l, _p, _l, _l, _i, _p, _i, _p]),
-    "rdst_u_maxpool_fwd": (_i, [_p, _l, _p, _l, _p, _i, _i, _i, _i, _i, _p]),
-    "rdst_u_maxpool_bwd": (_i, [_p, _l, _p, _p, _l, _p, _l, _i, _i, _i, _i, _i, _p]),
-    "rdst_u_sumpool2": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _i, _i, _p]),
-    "rdst_u_pair_loss_fwd": (_i, [_p, _l, _p, _l, _l, _i, _i, _f, _i, _p, _p, _i, _p]),
-    "rdst_u_pair_loss_bwd": (_i, [_p, _l, _p, _l, _l, _i, _i, _f, _p, _p, _l, _p, _l, _i, _p]),
-    "rdst_u_dice_fwd": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _f, _f, _i, _p, _p, _p, _i, _p]),
-    "rdst_u_dice_bwd": (_i, [_p, _l, _p, _l, _p, _l, _i, _p, _p, _p, _l, _i, _i, _p]),
-    # PSNR / SSIM scoring (rdst_amd.metrics.device_scores)
-    "rdst_sr_scores_workspace": (_z, [_i, _i, _i, _i, _i, _i]),
-    "rdst_sr_scores": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, C.c_double, _p, _p, _p, _z, _p]),
-    # bicubic degradation and the training-batch sampler (rdst_amd.data)
-    "rdst_resize_bicubic": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
-    "rdst_sample_patches": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
-    "rdst_sample_patches_d8": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
-    # tiled whole-slice inference (rdst_amd.tiling)
-    "rdst_unfold_tiles": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _l, _i, _p]),
-    "rdst_fold_tiles": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "rdst_unfold_tiles_d8": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _l, _i, _p]),
-    "rdst_merge_tiles_d8": (_i, [_p, _p, _i, _i, _i, _p]),
-    # the device-side step guard (rdst_amd.optim.FlatAdam(device_state=True))
-    "rdst_step_guard_workspace": (_z, [_l]),
-    "rdst_step_guard": (_i, [_p, C.c_double, _p, _p, _l, C.c_double, _i, _p, _z, _p, _p]),
-    "rdst_adam_step_dev": (_i, [_p, _p, _p, _p, _l, LrSchedule, _f, _f, _f, _f, _p, _p]),
-    # the weight EMA (rdst_amd.optim.FlatAdam(ema_decay=...)): additive entry points, the ABI version stays
-    "rdst_adam_step_ema": (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _l, C.c_double, _i, _p]),
-    "rdst_adam_step_dev_ema": (_i, [_p, _p, _p, _p, _p, _l, LrSchedule, _f, _f, _f, _f, C.c_double, _i, _p, _p]),
-    "rdst_swap_f32": (_i, [_p, _p, _l, _p]),
-    # the SSIM training loss (rdst_amd.loss.ssim_loss): additive entry points, the ABI version stays
-    "rdst_ssim_loss_workspace": (_z, [_i, _i, _i, _i, _i]),
-    "rdst_ssim_loss": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, C.c_double, C.c_double, _p, _p, _p, _p, _z, _p]),
-}
+
+def _struct(name, body, structs):
+    fields = []
+    for stmt in filter(None, (" ".join(s.split()) for s in body.split(";"))):
+        first, *more = (d.strip() for d in stmt.split(","))    # `int N, K`: the type stands before the first declarator
+        m = re.fullmatch(r"(.+?)\s*\b(\w+)\s*(?:\[\s*(\d+)\s*\])?", first)
+        rest = [re.fullmatch(r"()(\w+)\s*(?:\[\s*(\d+)\s*\])?", d) for d in more]
+        if m is None or None in rest or (more and "*" in m[1]):
+            raise RuntimeError(f"rdst_amd: include/rdst_hip.h: cannot read the field '{stmt}' of struct {name}")
+        base = _ctype(m[1], _FIELD_SCALARS, structs, f"struct {name} {{ {stmt}; }}")
+        fields += [(d[2], base * int(d[3]) if d[3] else base) for d in (m, *rest)]
+    return type(name, (C.Structure,), {"_fields_": fields})
+
+
+def parse_header(text):
+    """(signatures, params, structs, constants) of a header text in the style of include/rdst_hip.h:
+    name -> (restype, [argtypes]), name -> parameter names, typedef name -> ctypes.Structure, and the RDST_* ``#define``s
+    whose value is an integer literal or a parenthesised negative one (without the prefix).  Strict: a declaration that
+    does not match, a type outside the map or a parameter without a name raises and names the declaration."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants, lines = {}, []
+    for line in text.splitlines():
+        if not line.lstrip().startswith("#"):
+            lines.append(line)
+        elif m := re.fullmatch(r"\s*#\s*define\s+RDST_(\w+)\s+(\d+|\(\s*-\s*\d+\s*\))\s*", line):
+            constants[m[1]] = int(re.sub(r"[()\s]", "", m[2]))
+    body = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", "\n".join(lines), flags=re.S)
+    structs = {}
+
+    def cut(m):
+        structs[m[2]] = _struct(m[2], m[1], structs)
+        return ""
+    body = re.sub(r"typedef\s+struct\s*\w*\s*\{(.*?)\}\s*(\w+)\s*;", cut, body, flags=re.S)
+    signatures, params = {}, {}
+    for decl in filter(None, (" ".join(d.split()) for d in body.split(";"))):
+        m = re.fullmatch(r"(.+?)\s*\b(\w+)\s*\((.*)\)", decl)
+        if m is None:
+            raise RuntimeError(f"rdst_amd: include/rdst_hip.h: not a function declaration: {decl}")
+        ret = re.sub(r"\s*\*", "*", m[1])
+        if ret not in _RETURNS:
+            raise RuntimeError(f"rdst_amd: include/rdst_hip.h: return type '{ret}' is not in the binding's type map, in: {decl}")
+        args = [] if m[3].strip() in ("", "void") else [re.fullmatch(r"(.+?)\s*\b(\w+)", a.strip()) for a in m[3].split(",")]
+        if None in args:
+            raise RuntimeError(f"rdst_amd: include/rdst_hip.h: a parameter without a name, in: {decl}")
+        signatures[m[2]] = (_RETURNS[ret], [_ctype(a[1], _SCALARS, structs, decl) for a in args])
+        params[m[2]] = tuple(a[2] for a in args)
+    return signatures, params, structs, constants
+
+
+def _read_header():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError(f"rdst_amd: {HEADER_PATH} is missing. The ctypes binding is derived from it "
+                           "(it ships beside the package, as in the repository); there is no second copy.")
+    with open(HEADER_PATH) as f:
+        return f.read()
+
+
+# name -> (restype, argtypes) and name -> parameter names of every symbol include/rdst_hip.h declares (PARAMS is for tests
+# and tools that pick arguments out of a call; the product path passes them by position)
+SIGNATURES, PARAMS, _structs, CONSTANTS = parse_header(_read_header())
+
+PackJob = _structs["rdst_pack_job"]
+LrSchedule = _structs["rdst_lr_schedule"]   # passed by value to rdst_adam_step_dev
+LrSchedule.MAX_MILESTONES = dict(LrSchedule._fields_)["milestones"]._length_
+StepState = _structs["rdst_step_state"]
+STEP_STATE_BYTES = C.sizeof(StepState)
+
+F32, BF16, F32X3 = (CONSTANTS[k] for k in ("F32", "BF16", "F32X3"))
+EINVAL, ENOTSUP = CONSTANTS["EINVAL"], CONSTANTS["ENOTSUP"]
+ACT_NONE, ACT_GELU, ACT_LEAKY02, ACT_LEAKY001 = (CONSTANTS[k] for k in ("ACT_NONE", "ACT_GELU", "ACT_LEAKY02", "ACT_LEAKY001"))
+SKIP_LOSS, SKIP_NONFINITE, SKIP_PEER = (CONSTANTS[k] for k in ("SKIP_LOSS", "SKIP_NONFINITE", "SKIP_PEER"))
 
 ABI_VERSION = 11             # must equal rdst_abi_version() of the loaded library (argument lists change between versions)
-PREPACKED = (1 << 64) - 1   # RDST_PREPACKED ((size_t)-1)
-
-
-class PackJob(C.Structure):   # rdst_pack_job
-    _fields_ = [("kind", _i), ("W", _p), ("gamma", _p), ("beta", _p), ("bias", _p), ("out", _p), ("N", _i), ("K", _i), ("s", _f)]
-
+PREPACKED = (1 << 64) - 1   # RDST_PREPACKED ((size_t)-1): not an integer literal, so stated here
 
 _lib = None
 

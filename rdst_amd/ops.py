@@ -281,7 +281,8 @@ class keep_pack_plan:
         return False
 
 
-PACK_LINEAR, PACK_CONV3_FWD, PACK_LINEAR_SEC3, PACK_LINEAR_X3, PACK_CONV3_FWD_X3 = 0, 1, 2, 3, 4
+PACK_LINEAR, PACK_CONV3_FWD, PACK_LINEAR_SEC3, PACK_LINEAR_X3, PACK_CONV3_FWD_X3 = (
+    _lib.CONSTANTS[k] for k in ("PACK_LINEAR", "PACK_CONV3_FWD", "PACK_LINEAR_SEC3", "PACK_LINEAR_X3", "PACK_CONV3_FWD_X3"))
 
 
 def _linear_pack_kind(code: int) -> int:
@@ -353,35 +354,61 @@ ATTN_FUSED = os.environ.get("RDST_ATTN_FUSED", "1") != "0"   # K8 (LayerNorm + q
 # ------------------------------------------------------------------------------------------------
 # K1 / K2: fused window attention
 # ------------------------------------------------------------------------------------------------
+def _wattn_fwd(lib, qkv, ld, tab, msk, out, geom, attn_drop=0.0, seed=None, try_lse=False):
+    """The one launch site of the window-attention forwards.  geom = (B, H, W, C, heads, ws, shift, scale, code); attn_drop > 0:
+    training-mode dropout keyed by seed; try_lse: ask rdst_wattn_fwd_lse first, and return its row statistics where it ran."""
+    B, H, W, C, heads = geom[:5]
+    if try_lse:
+        nlse = torch.empty((B * H * W, heads), dtype=torch.float32, device=qkv.device)
+        rc = lib.rdst_wattn_fwd_lse(qkv.data_ptr(), ld, tab.data_ptr(), out.data_ptr(), C, nlse.data_ptr(), *geom, _stream())
+        if rc != _lib.ENOTSUP:
+            _lib.check(rc, "rdst_wattn_fwd_lse")
+            return nlse
+    args = (qkv.data_ptr(), ld, tab.data_ptr(), _ptr(msk), 0 if msk is None else msk.shape[0], out.data_ptr(), C, *geom)
+    if attn_drop > 0.0:
+        _lib.check(lib.rdst_wattn_fwd_drop(*args, attn_drop, seed.data_ptr(), _stream()), "rdst_wattn_fwd_drop")
+    else:
+        _lib.check(lib.rdst_wattn_fwd(*args, _stream()), "rdst_wattn_fwd")
+    return None
+
+
+def _wattn_bwd(lib, qkv, ld, tab, msk, dout, ldd, dqkv, dtable, wsp, nbytes, geom, attn_drop=0.0, seed=None, saved=None):
+    """The one launch site of the window-attention backwards (arguments as _wattn_fwd; dqkv rows have ld = 3C; the workspace
+    is the caller's to park).  saved = (out, nlse) of a forward that kept them: rdst_wattn_bwd_lse, plain where it refuses."""
+    C = geom[3]
+    grads = (dqkv.data_ptr(), 3 * C, dtable.data_ptr(), wsp.data_ptr(), nbytes, *geom)
+    if saved is not None:
+        rc = lib.rdst_wattn_bwd_lse(qkv.data_ptr(), ld, tab.data_ptr(), dout.data_ptr(), ldd, saved[0].data_ptr(), C,
+                                    saved[1].data_ptr(), *grads, _stream())
+        if rc != _lib.ENOTSUP:
+            _lib.check(rc, "rdst_wattn_bwd_lse")
+            return
+    args = (qkv.data_ptr(), ld, tab.data_ptr(), _ptr(msk), 0 if msk is None else msk.shape[0], dout.data_ptr(), ldd, *grads)
+    if attn_drop > 0.0:
+        _lib.check(lib.rdst_wattn_bwd_drop(*args, attn_drop, seed.data_ptr(), _stream()), "rdst_wattn_bwd_drop")
+    else:
+        _lib.check(lib.rdst_wattn_bwd(*args, _stream()), "rdst_wattn_bwd")
+
+
 class _WindowAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, table, mask, H, W, heads, ws, shift, scale, attn_drop=0.0, seed=None):
         _need_gpu(qkv, table, mask)
-        lib = _lib.load()
         C = qkv.shape[-1] // 3
         B = qkv.numel() // (H * W * 3 * C)
         qkv_r, ld = _rows(qkv)
-        tab = _param(table)
-        msk = _param(mask)
-        nw = 0 if msk is None else msk.shape[0]
+        tab, msk = _param(table), _param(mask)
         out = torch.empty(qkv.shape[:-1] + (C,), dtype=qkv.dtype, device=qkv.device)
-        code = _dtype_code(qkv)
-        if attn_drop > 0.0:   # training-mode attention dropout: the shape-generic kernels with a counter-based mask
-            _lib.check(lib.rdst_wattn_fwd_drop(qkv_r.data_ptr(), ld, tab.data_ptr(), _ptr(msk), nw, out.data_ptr(), C, B, H,
-                                               W, C, heads, ws, shift, float(scale), code, float(attn_drop),
-                                               seed.data_ptr(), _stream()), "rdst_wattn_fwd_drop")
-        else:
-            _lib.check(lib.rdst_wattn_fwd(qkv_r.data_ptr(), ld, tab.data_ptr(), _ptr(msk), nw, out.data_ptr(), C, B, H,
-                                          W, C, heads, ws, shift, float(scale), code, _stream()),
-                       "rdst_wattn_fwd")
+        ctx.geom = (B, H, W, C, heads, ws, shift, float(scale), _dtype_code(qkv))
+        ctx.ld, ctx.attn_drop = ld, float(attn_drop)
+        _wattn_fwd(_lib.load(), qkv_r, ld, tab, msk, out, ctx.geom, ctx.attn_drop, seed)
         ctx.save_for_backward(qkv_r, tab, msk, seed)
-        ctx.geom = (B, H, W, C, heads, ws, shift, float(scale), ld, nw, float(attn_drop), code)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv, tab, msk, seed = ctx.saved_tensors
-        B, H, W, C, heads, ws, shift, scale, ld, nw, attn_drop, code = ctx.geom
+        B, H, W, C, heads, ws = ctx.geom[:6]
         lib = _lib.load()
         dout_r, ldd = _rows(dout)
         dqkv = torch.empty(qkv.shape[:-1] + (3 * C,), dtype=qkv.dtype, device=qkv.device)
@@ -390,15 +417,7 @@ class _WindowAttention(torch.autograd.Function):
         wsp = _workspace(nbytes, qkv.device)
         if _ReduceBatch.depth > 0:   # an outer batch is open: the d(table) slabs are summed when it ends
             _ReduceBatch.keep.append(wsp)
-        if attn_drop > 0.0:
-            _lib.check(lib.rdst_wattn_bwd_drop(qkv.data_ptr(), ld, tab.data_ptr(), _ptr(msk), nw, dout_r.data_ptr(), ldd,
-                                               dqkv.data_ptr(), 3 * C, dtable.data_ptr(), wsp.data_ptr(), nbytes, B, H, W,
-                                               C, heads, ws, shift, scale, code, attn_drop, seed.data_ptr(),
-                                               _stream()), "rdst_wattn_bwd_drop")
-        else:
-            _lib.check(lib.rdst_wattn_bwd(qkv.data_ptr(), ld, tab.data_ptr(), _ptr(msk), nw, dout_r.data_ptr(), ldd,
-                                          dqkv.data_ptr(), 3 * C, dtable.data_ptr(), wsp.data_ptr(), nbytes, B, H, W,
-                                          C, heads, ws, shift, scale, code, _stream()), "rdst_wattn_bwd")
+        _wattn_bwd(lib, qkv, ctx.ld, tab, msk, dout_r, ldd, dqkv, dtable, wsp, nbytes, ctx.geom, ctx.attn_drop, seed)
         _ReduceBatch.settle(lib)
         return dqkv, dtable, None, None, None, None, None, None, None, None, None
 
@@ -796,18 +815,9 @@ class _SwinBlock(torch.autograd.Function):
         nlse = None
         if not fused_attn:
             _ln_linear_fwd(lib, x_r, ldx, n1w_, n1b_, ACT_NONE, qkvw_, qkvb_, None, 0, qkv, 3 * C, stats1, M, C, 3 * C, 1.0, code)
-            if ATTN_LSE and ws == 16 and code == BF16:
-                # window 16: keep the row statistics, the backward's first pass then streams its key tiles (rdst_wattn_bwd_lse)
-                nlse = torch.empty((M, heads), dtype=torch.float32, device=dev)
-                rc = lib.rdst_wattn_fwd_lse(qkv.data_ptr(), 3 * C, tab_.data_ptr(), a.data_ptr(), C, nlse.data_ptr(), B, H, W, C,
-                                            heads, ws, shift, float(scale), code, _stream())
-                if rc == _lib.ENOTSUP:
-                    nlse = None
-                else:
-                    _lib.check(rc, "rdst_wattn_fwd_lse")
-            if nlse is None:
-                _lib.check(lib.rdst_wattn_fwd(qkv.data_ptr(), 3 * C, tab_.data_ptr(), None, 0, a.data_ptr(), C, B, H, W, C,
-                                              heads, ws, shift, float(scale), code, _stream()), "rdst_wattn_fwd")
+            # window 16: keep the row statistics, the backward's first pass then streams its key tiles (rdst_wattn_bwd_lse)
+            nlse = _wattn_fwd(lib, qkv, 3 * C, tab_, None, a, (B, H, W, C, heads, ws, shift, float(scale), code),
+                              try_lse=ATTN_LSE and ws == 16 and code == BF16)
             _ln_linear_fwd(lib, a, C, None, None, ACT_NONE, projw_, projb_, x_r, ldx, x1, C, None, M, C, C, 1.0, code)
         stats2 = torch.empty((M, 2), dtype=torch.float32, device=dev) if n2w_ is not None else None
         y = torch.empty(lead + (C,), dtype=dt, device=dev)
@@ -928,17 +938,8 @@ class _SwinBlock(torch.autograd.Function):
         nbytes = lib.rdst_wattn_bwd_workspace(B, H, W, C, heads, ws)
         wsp = _workspace(nbytes, dev)
         keep.append(wsp)
-        rc = _lib.ENOTSUP
-        if nlse is not None:   # window 16 with the forward's row statistics: the streaming first pass
-            rc = lib.rdst_wattn_bwd_lse(qkv.data_ptr(), 3 * C, tab.data_ptr(), da.data_ptr(), C, a.data_ptr(), C, nlse.data_ptr(),
-                                        dqkv.data_ptr(), 3 * C, dtab.data_ptr(), wsp.data_ptr(), nbytes, B, H, W, C, heads, ws,
-                                        shift, scale, code, _stream())
-            if rc != _lib.ENOTSUP:
-                _lib.check(rc, "rdst_wattn_bwd_lse")
-        if rc == _lib.ENOTSUP:
-            _lib.check(lib.rdst_wattn_bwd(qkv.data_ptr(), 3 * C, tab.data_ptr(), None, 0, da.data_ptr(), C,
-                                          dqkv.data_ptr(), 3 * C, dtab.data_ptr(), wsp.data_ptr(), nbytes, B, H, W, C,
-                                          heads, ws, shift, scale, code, _stream()), "rdst_wattn_bwd")
+        _wattn_bwd(lib, qkv, 3 * C, tab, None, da, C, dqkv, dtab, wsp, nbytes, (B, H, W, C, heads, ws, shift, scale, code),
+                   saved=None if nlse is None else (a, nlse))
         # LN1 + qkv, plus the residual fan-out of x:  dx = dx1 + LN1'(dqkv Wqkv)
         dx = torch.empty(x.shape, dtype=dt, device=dev) if need[0] else None
         extra = ctx.sink.take() if ctx.sink is not None else None   # the dense join's gradient slice for x (GradSink)

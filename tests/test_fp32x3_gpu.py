@@ -559,16 +559,20 @@ def test_e1_fp32x3_train_step_48x40_slice_vs_oracle():
 # ------------------------------------------------------------------------------------------------------------------
 # Shape census: the suite follows the benchmark's shapes
 # ------------------------------------------------------------------------------------------------------------------
-# argument positions in include/rdst_hip.h -> (shape signature, compute code)
+# a call's arguments, by the parameter names of include/rdst_hip.h -> (shape signature, compute code)
 _CENSUS = {
-    "rdst_ln_linear_fwd": lambda a: (("lin", a[15], a[16], int(a[2] is not None), a[4], int(a[7] is not None),
-                                      int(a[5] is not None)), a[18]),
-    "rdst_ln_linear_bwd": lambda a: (("lin_bwd", a[20], a[21], int(a[2] is not None), a[5], int(a[6] is not None)), a[23]),
-    "rdst_ln_linear_bwd2": lambda a: (("lin_bwd", a[20], a[21], int(a[2] is not None), a[5], int(a[6] is not None)), a[23]),
-    "rdst_conv_fwd": lambda a: (("conv", a[12], a[13], a[14], a[15], a[16], a[18], int(a[5] is not None), a[2]), a[19]),
-    "rdst_conv_bwd": lambda a: (("conv_bwd", a[15], a[16], a[17], a[18], a[19], a[21], a[2]), a[22]),
-    "rdst_wattn_fwd": lambda a: (("attn", a[8], a[9], a[10], a[11], a[12], a[13]), a[15]),
-    "rdst_wattn_bwd": lambda a: (("attn", a[13], a[14], a[15], a[16], a[17], a[18]), a[20]),
+    "rdst_ln_linear_fwd": lambda a: (("lin", a("K"), a("N"), int(a("ln_w") is not None), a("in_act"), int(a("R") is not None),
+                                      int(a("Wt") is not None)), a("dtype")),
+    "rdst_ln_linear_bwd": lambda a: (("lin_bwd", a("K"), a("N"), int(a("ln_w") is not None), a("in_act"),
+                                      int(a("Wt") is not None)), a("dtype")),
+    "rdst_ln_linear_bwd2": lambda a: (("lin_bwd", a("K"), a("N"), int(a("ln_w") is not None), a("in_act"),
+                                       int(a("Wt") is not None)), a("dtype")),
+    "rdst_conv_fwd": lambda a: (("conv", a("H"), a("W"), a("Cin"), a("Cout"), a("ksize"), a("shuffle_r"), int(a("R") is not None),
+                                 a("in_act")), a("dtype")),
+    "rdst_conv_bwd": lambda a: (("conv_bwd", a("H"), a("W"), a("Cin"), a("Cout"), a("ksize"), a("shuffle_r"), a("in_act")),
+                                a("dtype")),
+    "rdst_wattn_fwd": lambda a: (("attn", a("H"), a("W"), a("C"), a("heads"), a("ws"), a("shift")), a("dtype")),
+    "rdst_wattn_bwd": lambda a: (("attn", a("H"), a("W"), a("C"), a("heads"), a("ws"), a("shift")), a("dtype")),
 }
 
 
@@ -588,8 +592,8 @@ def test_e1_fp32x3_shape_census(monkeypatch):
     lib = _lib.load()
     seen = {}
     for name, sig in _CENSUS.items():
-        def wrapped(*a, _f=getattr(lib, name), _sig=sig, _name=name):
-            seen.setdefault(_sig(a), set()).add(_name)
+        def wrapped(*a, _f=getattr(lib, name), _sig=sig, _name=name, _at={p: i for i, p in enumerate(_lib.PARAMS[name])}):
+            seen.setdefault(_sig(lambda p: a[_at[p]]), set()).add(_name)
             return _f(*a)
         monkeypatch.setattr(lib, name, wrapped)
     _e1_step("fp32x3", B=2)

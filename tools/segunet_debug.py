@@ -3,6 +3,7 @@ import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, torch.nn.functional as F
 from oracle import segunet_oracle as S
+from rdst_amd import _lib
 from rdst_amd.loss import seg_unet as U
 
 mode = sys.argv[1] if len(sys.argv) > 1 else "decoder"
@@ -50,9 +51,10 @@ def tapped(self, save, d_feats, d_dec=None, upstream=None):
     lib = self.lib
     real = lib.rdst_u_sumpool2
     cnt = [0]
+    at = {p: i for i, p in enumerate(_lib.PARAMS["rdst_u_sumpool2"])}
     def sp(*a):
         rc = real(*a)
-        taps[f"dprev{cnt[0]}"] = (a[4], a[6:10])   # dX ptr, B,H,W,C
+        taps[f"dprev{cnt[0]}"] = (a[at["dX"]], tuple(a[at[p]] for p in "BHWC"))
         cnt[0] += 1
         return rc
     lib.rdst_u_sumpool2 = sp
