@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # is the in-tree release library, and a missing file raises either way
 LIB_PATH = os.environ.get("RDST_HIP_LIB") or os.path.join(_HERE, "librdst_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rdst_hip.h")
+DATA_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rdst_hip_data.h")   # the K-tap degradations (data.py)
 
 _SCALARS = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
 _FIELD_SCALARS = {**_SCALARS, "int32_t": C.c_int32}
@@ -82,17 +83,21 @@ def parse_header(text):
     return signatures, params, structs, constants
 
 
-def _read_header():
-    if not os.path.exists(HEADER_PATH):
-        raise RuntimeError(f"rdst_amd: {HEADER_PATH} is missing. The ctypes binding is derived from it "
+def _read_header(path=None):
+    path = path or HEADER_PATH
+    if not os.path.exists(path):
+        raise RuntimeError(f"rdst_amd: {path} is missing. The ctypes binding is derived from it "
                            "(it ships beside the package, as in the repository); there is no second copy.")
-    with open(HEADER_PATH) as f:
+    with open(path) as f:
         return f.read()
 
 
 # name -> (restype, argtypes) and name -> parameter names of every symbol include/rdst_hip.h declares (PARAMS is for tests
 # and tools that pick arguments out of a call; the product path passes them by position)
 SIGNATURES, PARAMS, _structs, CONSTANTS = parse_header(_read_header())
+
+# the same of include/rdst_hip_data.h: entry points outside ABI_VERSION's count (a library without them gets raisers)
+DATA_SIGNATURES, DATA_PARAMS, _, _ = parse_header(_read_header(DATA_HEADER_PATH))
 
 PackJob = _structs["rdst_pack_job"]
 LrSchedule = _structs["rdst_lr_schedule"]   # passed by value to rdst_adam_step_dev
@@ -121,7 +126,7 @@ def load() -> C.CDLL:
             f"rdst_amd: {LIB_PATH} is missing. Build it with `python -m rdst_amd.build` "
             "(hipcc --offload-arch=gfx950); there is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **DATA_SIGNATURES}.items():
         fn = getattr(lib, name, None)
         if fn is None:  # a declared symbol the .so does not export: calling it raises
             setattr(lib, name, _missing(name))

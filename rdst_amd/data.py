@@ -7,6 +7,8 @@ slices (``get_test_pair``, basic_dataset.py:258-301).  The training volumes fit 
 slices are moved to the GPU once and a batch is cut and degraded where it is consumed:
 
   * ``bicubic_resize(x, size)``      the resize itself (rdst_resize_bicubic, include/rdst_hip.h);
+  * ``resample(x, size, degradation)``  the same under any ``Degradation``: a separable linear operator given as a table of K
+                                     taps per output (``operator_table``; rdst_resample_sep, include/rdst_hip_data.h);
   * ``make_test_pair(hr, s)``        ``get_test_pair`` for one scale: what ``SRTester.evaluate`` / ``DPTrainStep.quick_eva`` take;
   * ``DevicePatchSampler``           ``__getitem__``: one HIP launch per batch (rdst_sample_patches), three random integers per
                                      patch drawn on the host, nothing read back; ``DPTrainStep.step_from(sampler)`` trains on it.
@@ -21,13 +23,19 @@ source coordinate ``(dst + 0.5) * in / out - 0.5``, tap indices clamped to the i
 overshoot below 0 and above 1 is kept, basic_dataset.py:74).  **cv2 is not installed in the build image**: the tests pin the
 resize to torch's float64 bicubic, and equality with cv2 is argued from its documented algorithm, not tested.
 
-Out of scope, and refused where they could be asked for: the Gaussian blur option (``blur_method='gaussian'``,
-cv2.GaussianBlur), augmentation other than the eight flips / transposes, ``return_res_image``, reading volumes from disk.
+Degradations (``Degradation``, ``operator_table``): ``'cubic'`` is the resize above; ``'cubic+gaussian'`` the reference's
+``blur_method='gaussian'`` (cv2.GaussianBlur of the resized image, basic_dataset.py:112-116); ``'cubic_aa'`` the antialiased
+bicubic of Pillow / ``interpolate(antialias=True)`` behind the SwinIR / EDSR benchmark sets; ``'fourier'`` k-space truncation,
+the low-resolution acquisition of MR slices.  Each is ``LR = A_y . patch . A_x^T`` with K taps per output; the sampler, the
+whole-image resample and the test pair take any of them through one K-tap kernel family (csrc/resample.hip).
+
+Out of scope, and refused where they could be asked for: augmentation other than the eight flips / transposes,
+``return_res_image``, reading volumes from disk.
 """
 from __future__ import annotations
 
 import math
-from typing import Dict, NamedTuple, Optional, Sequence, Tuple
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -70,6 +78,214 @@ def _device_table(n_in: int, n_out: int, device: torch.device) -> Tuple[torch.Te
         index, weight = tap_table(n_in, n_out)
         tab = (torch.from_numpy(index).to(device), torch.from_numpy(weight.astype(np.float32)).to(device))
         _TABLES[key] = tab
+    return tab
+
+
+# ---- degradations as K-tap tables ------------------------------------------------------------------------------------------
+KINDS = ("cubic", "cubic+gaussian", "cubic_aa", "fourier")
+A_KEYS_AA = -0.5   # the cubic-convolution parameter of Pillow's BICUBIC and of torch's antialiased bicubic
+# cv2.getGaussianKernel's fixed tables for sigma <= 0 (ksize 3, 5, 7)
+_CV2_SMALL_GAUSSIAN = {3: (0.25, 0.5, 0.25), 5: (0.0625, 0.25, 0.375, 0.25, 0.0625),
+                       7: (0.03125, 0.109375, 0.21875, 0.28125, 0.21875, 0.109375, 0.03125)}
+_OPTS = {"cubic": {}, "cubic+gaussian": {"blur_kernel": 3, "blur_sigma": 0.0}, "cubic_aa": {}, "fourier": {}}
+
+
+class Degradation:
+    """How an HR patch becomes its LR input: ``Degradation(kind='cubic', **opts)``, a frozen, hashable value.  A plain string
+    is accepted wherever a ``Degradation`` is.  Kinds and options: ``'cubic'``; ``'cubic+gaussian'`` (``blur_kernel=3``: odd,
+    3..7; ``blur_sigma=0``: cv2's fixed kernel if <= 0); ``'cubic_aa'``; ``'fourier'``.  ``operator_table`` defines them."""
+    __slots__ = ("kind", "opts")
+
+    def __init__(self, kind: str = "cubic", **opts):
+        if kind not in KINDS:
+            raise ValueError(f"Degradation: kind={kind!r} is not one of {KINDS}")
+        known = _OPTS[kind]
+        for k in opts:
+            if k not in known:
+                raise ValueError(f"Degradation: {kind!r} takes no option {k!r} (it takes {tuple(known) or 'none'})")
+        full = {**known, **opts}
+        if kind == "cubic+gaussian":
+            bk = full["blur_kernel"]
+            if isinstance(bk, bool) or not isinstance(bk, (int, np.integer)) or bk % 2 == 0 or not 3 <= bk <= 7:
+                raise ValueError(f"Degradation: blur_kernel={bk!r} must be odd and in 3..7")
+            sg = float(full["blur_sigma"])
+            if not math.isfinite(sg):
+                raise ValueError(f"Degradation: blur_sigma={full['blur_sigma']!r} must be finite")
+            full = {"blur_kernel": int(bk), "blur_sigma": sg}
+        object.__setattr__(self, "kind", kind)
+        object.__setattr__(self, "opts", tuple(sorted(full.items())))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Degradation is frozen")
+
+    __delattr__ = __setattr__
+
+    def __eq__(self, other):
+        return isinstance(other, Degradation) and (self.kind, self.opts) == (other.kind, other.opts)
+
+    def __hash__(self):
+        return hash((self.kind, self.opts))
+
+    def __repr__(self):
+        return "Degradation(" + ", ".join([repr(self.kind)] + [f"{k}={v!r}" for k, v in self.opts]) + ")"
+
+    @classmethod
+    def of(cls, d: Union["Degradation", str]) -> "Degradation":
+        if isinstance(d, Degradation):
+            return d
+        if isinstance(d, str):
+            return cls(d)
+        raise TypeError(f"a degradation is a Degradation or the name of a kind, not {type(d).__name__}")
+
+    @classmethod
+    def from_paras(cls, paras) -> "Degradation":
+        """``paras.blur_method`` of the reference's configuration (``None`` / ``''`` / ``'gaussian'``) as a ``Degradation``.
+        ``paras.blur_kernel`` / ``paras.blur_sigma`` are taken where they exist."""
+        bm = getattr(paras, "blur_method", None)
+        if bm in (None, ""):
+            return cls("cubic")
+        if bm == "gaussian":
+            opts = {k: getattr(paras, k) for k in ("blur_kernel", "blur_sigma") if getattr(paras, k, None) is not None}
+            return cls("cubic+gaussian", **opts)
+        raise ValueError(f"Degradation.from_paras: blur_method={bm!r} is not None, '' or 'gaussian'")
+
+
+def _keys(x: np.ndarray, a: float) -> np.ndarray:
+    """The cubic-convolution kernel of Keys with parameter ``a``."""
+    x = np.abs(x)
+    near = ((a + 2) * x - (a + 3)) * x * x + 1
+    far = ((a * x - 5 * a) * x + 8 * a) * x - 4 * a
+    return np.where(x < 1, near, np.where(x < 2, far, 0.0))
+
+
+def _reflect101(p: int, n: int) -> int:
+    """cv2's BORDER_REFLECT_101 (-1 -> 1, n -> n - 2), repeated until the index is inside."""
+    while p < 0 or p >= n:
+        p = -p if p < 0 else 2 * n - 2 - p
+    return p
+
+
+def _cubic_matrix(n_in: int, n_out: int) -> np.ndarray:
+    index, weight = tap_table(n_in, n_out)
+    R = np.zeros((n_out, n_in))
+    np.add.at(R, (np.arange(n_out)[:, None], index), weight)      # clamped taps meet on the border sample
+    return R
+
+
+def _gaussian_matrix(n: int, blur_kernel: int, blur_sigma: float) -> np.ndarray:
+    if blur_sigma <= 0:
+        g = np.array(_CV2_SMALL_GAUSSIAN[blur_kernel])
+    else:
+        d = np.arange(blur_kernel, dtype=np.float64) - (blur_kernel - 1) / 2
+        g = np.exp(-(d * d) / (2.0 * blur_sigma * blur_sigma))
+        g /= g.sum()
+    G, half = np.zeros((n, n)), blur_kernel // 2
+    for o in range(n):
+        for t in range(blur_kernel):
+            G[o, _reflect101(o + t - half, n)] += g[t]
+    return G
+
+
+def _aa_matrix(n_in: int, n_out: int) -> np.ndarray:
+    scale = n_in / n_out
+    s = max(scale, 1.0)
+    M = np.zeros((n_out, n_in))
+    for o in range(n_out):
+        c = scale * (o + 0.5)
+        lo, hi = max(int(c - 2 * s + 0.5), 0), min(int(c + 2 * s + 0.5), n_in)
+        w = _keys((np.arange(lo, hi) + 0.5 - c) / s, A_KEYS_AA)
+        M[o, lo:hi] = w / w.sum()
+    return M
+
+
+def _fourier_matrix(n_in: int, n_out: int) -> np.ndarray:
+    X = np.fft.rfft(np.eye(n_in), axis=0)           # column i: the spectrum of the unit sample i
+    Y = X[:n_out // 2 + 1].copy()
+    if n_out % 2 == 0 and n_out < n_in:
+        Y[n_out // 2] *= 2.0
+    return np.fft.irfft(Y, n_out, axis=0) * (n_out / n_in)
+
+
+def _table_of(M: np.ndarray, support: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """A matrix (n_out, n_in) and the boolean mask of its taps -> ``(index, weight)`` of K columns."""
+    counts = support.sum(axis=1)
+    if counts.min() < 1:
+        raise ValueError("operator_table: an output without taps")
+    K = max(4, -(-int(counts.max()) // 4) * 4)
+    index = np.empty((M.shape[0], K), dtype=np.int32)
+    weight = np.zeros((M.shape[0], K), dtype=np.float64)
+    for o in range(M.shape[0]):
+        j = np.flatnonzero(support[o])
+        index[o, :len(j)], index[o, len(j):] = j, j[-1]
+        weight[o, :len(j)] = M[o, j]
+    return index, weight
+
+
+def operator_table(kind: Union[str, Degradation], n_in: int, n_out: int, **opts) -> Tuple[np.ndarray, np.ndarray]:
+    """The 1-D operator of a degradation along an axis of ``n_in`` samples, ``n_out`` outputs: ``(index, weight)``, int32 and
+    float64 ``(n_out, K)``.  Taps stand in ascending source order, every source sample once (taps that clamping or reflection
+    puts on one sample are merged), K is the longest row's number of taps rounded up to a multiple of 4, and a shorter row is
+    padded at its end with weight 0.0 and its last real index.  ``kind`` is a name with its options, or a ``Degradation``.
+
+    ``'cubic'``: ``tap_table``, as it is (K = 4, border taps not merged).
+
+    ``'cubic+gaussian'``: ``G . R``, formed in float64: ``R`` the cubic operator ``n_in -> n_out`` and ``G`` the ``n_out x
+    n_out`` blur ``cv2.GaussianBlur(img, (k, k), sigma)`` applies to the RESIZED image (basic_dataset.py:112-116): ``k =
+    blur_kernel`` taps, border BORDER_REFLECT_101 (cv2's default: index -1 -> 1, n -> n - 2), weights cv2's fixed tables for
+    ``sigma <= 0`` ([1 2 1] / 4, [1 4 6 4 1] / 16, [4 14 28 36 28 14 4] / 128: getGaussianKernel's small_gaussian_tab, used
+    for ksize <= 7) and the normalised ``exp(-(i - c)^2 / (2 sigma^2))`` otherwise.  cv2.GaussianBlur is separable with that
+    kernel on both axes, so the blurred resize is ``(G_y R_y) patch (G_x R_x)^T``.  **cv2 is not installed in the build
+    image**: as for the resize, equality with cv2 is argued from its documented algorithm, and the tests pin the operator to
+    a reflect-padded convolution of torch's float64 bicubic.  (cv2 rounds the resized image to fp32 before it blurs and sums in
+    its own order; this operator rounds once, at the end.)  ``n_out < 2`` is refused (the border needs two samples).
+
+    ``'cubic_aa'``: what ``F.interpolate(mode='bicubic', align_corners=False, antialias=True)`` and Pillow's BICUBIC compute.
+    With ``scale = n_in / n_out``, ``s = max(scale, 1)`` and ``c = scale (o + 0.5)``, output ``o`` takes the samples ``lo =
+    max(int(c - 2 s + 0.5), 0) .. hi = min(int(c + 2 s + 0.5), n_in)`` (exclusive) with the weights ``keys((j + 0.5 - c) / s)``,
+    a = -0.5, divided by their sum: the window is cut at the border and renormalised, not clamped.  Samples of weight exactly
+    0 (the window's ends) are not taps.
+
+    ``'fourier'``: band-limited resampling, ``scipy.signal.resample``'s definition for real signals: the ``rfft`` of the axis,
+    bins ``0 .. n_out // 2`` kept, the bin ``n_out // 2`` doubled when ``n_out`` is even and below ``n_in`` (it stands for the
+    +- Nyquist pair of the short signal, so the operator is real), ``irfft`` to ``n_out`` samples, times ``n_out / n_in``.
+    Dense: every sample is a tap, K = ``n_in`` rounded up to a multiple of 4; every row sums to 1.  Only ``n_out <= n_in``.
+    A raw centred crop of k-space (``fftshift``, keep the middle ``n_out``, inverse transform) differs for even ``n_out``: it
+    keeps the -Nyquist row alone, without its partner, so its result is complex and its real part carries half of that bin."""
+    d = Degradation(kind, **opts) if isinstance(kind, str) else Degradation.of(kind)
+    if not isinstance(kind, str) and opts:
+        raise ValueError("operator_table: options go with a kind's name, not with a Degradation")
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in <= 0 or n_out <= 0:
+        raise ValueError(f"operator_table: sizes must be positive, got {n_in} -> {n_out}")
+    o = dict(d.opts)
+    if d.kind == "cubic":
+        return tap_table(n_in, n_out)
+    if d.kind == "cubic+gaussian":
+        if n_out < 2:
+            raise ValueError(f"operator_table: 'cubic+gaussian' needs at least 2 outputs (BORDER_REFLECT_101), got {n_out}")
+        R, G = _cubic_matrix(n_in, n_out), _gaussian_matrix(n_out, o["blur_kernel"], o["blur_sigma"])
+        return _table_of(G @ R, ((G != 0).astype(np.int64) @ (R != 0).astype(np.int64)) > 0)
+    if d.kind == "cubic_aa":
+        M = _aa_matrix(n_in, n_out)
+        return _table_of(M, M != 0)
+    if n_out > n_in:
+        raise ValueError(f"operator_table: 'fourier' only shrinks, got {n_in} -> {n_out}")
+    M = _fourier_matrix(n_in, n_out)
+    return _table_of(M, np.ones(M.shape, dtype=bool))
+
+
+_OP_TABLES: Dict[tuple, Tuple[torch.Tensor, torch.Tensor]] = {}
+
+
+def _device_op_table(d: Degradation, n_in: int, n_out: int, device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``operator_table`` on the device, the weights rounded once to fp32; cached per (kind, options, in, out, device)."""
+    key = (d, int(n_in), int(n_out), device.type, device.index)
+    tab = _OP_TABLES.get(key)
+    if tab is None:
+        index, weight = operator_table(d, n_in, n_out)
+        tab = (torch.from_numpy(np.ascontiguousarray(index)).to(device),
+               torch.from_numpy(weight.astype(np.float32)).to(device))
+        _OP_TABLES[key] = tab
     return tab
 
 
@@ -120,17 +336,54 @@ def bicubic_resize(x: torch.Tensor, size) -> torch.Tensor:
     return y[0] if squeeze else y
 
 
-def make_test_pair(hr: torch.Tensor, s: float):
+def resample(x: torch.Tensor, size, degradation: Union[str, Degradation] = "cubic") -> torch.Tensor:
+    """``bicubic_resize`` under any degradation: fp32 CUDA ``(N, C, H, W)`` (or ``(C, H, W)``) -> a new tensor of spatial
+    ``size``, the operator ``operator_table(degradation, H, oh)`` along the rows and ``(W, ow)`` along the columns
+    (rdst_resample_sep: the horizontal sums, then the vertical chains).  With ``'cubic'`` it gives ``bicubic_resize``'s bits.
+    Not differentiable."""
+    d = Degradation.of(degradation)
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("resample: x must be a torch tensor")
+    _need_gpu("resample", x)
+    if x.requires_grad:
+        raise RuntimeError("resample is not differentiable: detach the input")
+    if x.dtype != torch.float32:
+        raise TypeError(f"resample: x must be float32, got {x.dtype}")
+    squeeze = x.dim() == 3
+    if squeeze:
+        x = x.unsqueeze(0)
+    if x.dim() != 4:
+        raise ValueError("resample: x must have 3 or 4 dimensions")
+    oh, ow = _pair(size)
+    N, C, H, W = x.shape
+    if min(N, C, H, W) <= 0 or oh <= 0 or ow <= 0:
+        raise ValueError(f"resample: sizes must be positive, got {tuple(x.shape)} -> {(oh, ow)}")
+    x = x.contiguous()
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        iy, wy = _device_op_table(d, H, oh, x.device)
+        ix, wx = _device_op_table(d, W, ow, x.device)
+        y = torch.empty(N, C, oh, ow, dtype=torch.float32, device=x.device)
+        tmp = torch.empty(N * C * H * ow, dtype=torch.float32, device=x.device)
+        _lib.check(lib.rdst_resample_sep(x.data_ptr(), y.data_ptr(), tmp.data_ptr(), N, C, H, W, oh, ow, iy.shape[1],
+                                         iy.data_ptr(), wy.data_ptr(), ix.shape[1], ix.data_ptr(), wx.data_ptr(), _stream()),
+                   "rdst_resample_sep")
+    return y[0] if squeeze else y
+
+
+def make_test_pair(hr: torch.Tensor, s: float, degradation: Union[None, str, Degradation] = None):
     """``get_test_pair`` (datasets/basic_dataset.py:258-301) for one scale, on the device: ``hr`` fp32 CUDA ``(N, C, H, W)``
     -> ``(lr, gt, real_sr_scale)`` with ``lr = resize(hr, (H // s, W // s))``, ``gt = hr`` itself if ``(int(lr_h * s),
-    int(lr_w * s)) == (H, W)`` else ``resize(hr, that size)`` (:276), and the real scale of :286."""
+    int(lr_w * s)) == (H, W)`` else ``resize(hr, that size)`` (:276), and the real scale of :286.  ``degradation``: ``None``
+    the plain cubic resize above; otherwise ``lr = resample(hr, (H // s, W // s), degradation)``, while ``gt``, where it needs
+    a resize, stays the plain cubic one (the reference blurs the LR image only, :276 against :112-116)."""
     if hr.dim() != 4:
         raise ValueError("make_test_pair: hr must be (N, C, H, W)")
     H, W = hr.shape[-2:]
     lr_h, lr_w = int(H // s), int(W // s)
     if lr_h <= 0 or lr_w <= 0:
         raise ValueError(f"make_test_pair: a {H} x {W} slice is too small for scale {s}")
-    lr = bicubic_resize(hr, (lr_h, lr_w))
+    lr = bicubic_resize(hr, (lr_h, lr_w)) if degradation is None else resample(hr, (lr_h, lr_w), degradation)
     gh, gw = int(lr_h * s), int(lr_w * s)
     gt = hr if (gh, gw) == (H, W) else bicubic_resize(hr, (gh, gw))
     return lr, gt, (gh / lr_h, gw / lr_w)
@@ -206,14 +459,24 @@ class DevicePatchSampler:
     batch).  A ``draw=`` decides: ``Draw(..., variants=t)`` forces the transforms as it forces the origins, whatever
     ``augment`` is, and a draw without variants gives a plain batch.
 
+    ``degradation``: ``None`` / ``'cubic'`` the sampler above, bit for bit; any other ``Degradation`` (or its name) makes
+    ``in[b]`` that degradation of the cut and turned patch, still in one launch (rdst_sample_patches_op), with or without
+    ``augment`` and ``labels`` and for every scale (one table per ``(hp, lp)``): ``in == resample(out, lp, degradation)`` bit
+    for bit, ``out`` / ``label`` and the generator's use are unchanged, and the batch carries ``batch['degradation']``.
+    ``blur_method`` stays the reference's argument and is still refused unless ``None`` / ``''``: the Gaussian blur is asked
+    for with ``degradation='cubic+gaussian'`` or ``Degradation.from_paras(paras)``.
+
     ``device='cpu'`` keeps the slices on the host: ``draw()`` works, ``sample()`` raises (there is no CPU path)."""
 
     def __init__(self, hr_images, batch_size: int, lr_patch_size: int, sr_scales: Sequence[float] = (4.0,), labels=None,
                  blur_method: Optional[str] = None, device="cuda", generator: Optional[torch.Generator] = None,
-                 augment=False):
+                 augment=False, degradation: Union[None, str, Degradation] = None):
         if blur_method not in (None, ""):
-            raise ValueError(f"DevicePatchSampler: blur_method={blur_method!r} is not supported (cv2.GaussianBlur is out of "
-                             "scope; the shipped configuration has blur_method = '')")
+            raise ValueError(f"DevicePatchSampler: blur_method={blur_method!r} is not taken here: pass "
+                             "degradation='cubic+gaussian' (cv2.GaussianBlur of the resized patch) or "
+                             "degradation=Degradation.from_paras(paras); the shipped configuration has blur_method = ''")
+        d = None if degradation is None else Degradation.of(degradation)
+        self.degradation = None if d is None or d.kind == "cubic" else d     # None: the two 4-tap entry points, as before
         if not isinstance(augment, (bool, str, type(None))) or augment not in _AUGMENT:
             raise ValueError(f"DevicePatchSampler: augment={augment!r} is not one of False, True, 'd8', 'flip'")
         self.n_variants = _AUGMENT[augment]
@@ -224,6 +487,9 @@ class DevicePatchSampler:
         self.hr_patch_sizes = [int(self.lr_patch_size * s) for s in self.sr_scales]     # get_hr_patch_size
         if min(self.hr_patch_sizes) <= 0:
             raise ValueError(f"DevicePatchSampler: scales {self.sr_scales} give an empty HR patch")
+        if self.degradation is not None:
+            for hp in self.hr_patch_sizes:       # refuse what the operator refuses here, not at the first batch
+                operator_table(self.degradation, hp, self.lr_patch_size)
         hr = _as_stack(hr_images, "hr_images", True).to(torch.float32)
         if hr.shape[0] < self.batch_size:
             raise ValueError(f"DevicePatchSampler: {hr.shape[0]} slices cannot give {self.batch_size} distinct ones per batch")
@@ -320,18 +586,26 @@ class DevicePatchSampler:
             lab = None
             if self.labels is not None:
                 lab = torch.empty(hr_shape[0], 1, hp, hp, dtype=torch.uint8, device=self.device)
-            ti, tw = _device_table(hp, lp, self.device)
-            tail = (hr.data_ptr(), lr.data_ptr(), lab.data_ptr() if lab is not None else None, self.S, self.C, self.H, self.W,
-                    self.batch_size, hp, lp, ti.data_ptr(), tw.data_ptr(), _stream())
             stack, labels = self.hr_images.data_ptr(), self.labels.data_ptr() if lab is not None else None
-            if variant is None:
-                _lib.check(lib.rdst_sample_patches(stack, labels, index.data_ptr(), *tail), "rdst_sample_patches")
+            sizes = (hr.data_ptr(), lr.data_ptr(), lab.data_ptr() if lab is not None else None, self.S, self.C, self.H, self.W,
+                     self.batch_size, hp, lp)
+            if self.degradation is not None:
+                ti, tw = _device_op_table(self.degradation, hp, lp, self.device)
+                _lib.check(lib.rdst_sample_patches_op(stack, labels, index.data_ptr(), variant, *sizes, ti.shape[1],
+                                                      ti.data_ptr(), tw.data_ptr(), _stream()), "rdst_sample_patches_op")
             else:
-                _lib.check(lib.rdst_sample_patches_d8(stack, labels, index.data_ptr(), variant, *tail),
-                           "rdst_sample_patches_d8")
+                ti, tw = _device_table(hp, lp, self.device)
+                tail = (*sizes, ti.data_ptr(), tw.data_ptr(), _stream())
+                if variant is None:
+                    _lib.check(lib.rdst_sample_patches(stack, labels, index.data_ptr(), *tail), "rdst_sample_patches")
+                else:
+                    _lib.check(lib.rdst_sample_patches_d8(stack, labels, index.data_ptr(), variant, *tail),
+                               "rdst_sample_patches_d8")
         batch = {"in": lr, "out": hr, "sr_factor": d.sr_factor, "real_sr_scale": hp / lp, "indices": d.indices}
         if d.variants is not None:
             batch["variants"] = d.variants
+        if self.degradation is not None:
+            batch["degradation"] = self.degradation
         if lab is not None:
             batch["label"] = lab.to(torch.int64)          # the dtype SegUNet_F('label-gt') takes
         return batch

@@ -303,7 +303,9 @@ class DPTrainStep:
         captured and the batch has its shapes, the sampler writes straight into the tensors the graph reads, so ``step()``
         finds them in place and copies nothing; the sampler's launch is on the stream of the replay, so the previous replay
         has finished reading them.  Labels stay in the batch for the caller's own loop: ``step()`` takes none.  An augmenting
-        sampler (``augment=True``) is taken as it is: its transformed batch lands in the same tensors."""
+        sampler (``augment=True``) is taken as it is: its transformed batch lands in the same tensors.  So is a sampler with a
+        ``degradation`` (blurred, antialiased or Fourier-truncated inputs): the batch has the same shapes and nothing here
+        depends on how ``'in'`` was made."""
         draw = sampler.draw()
         out = None
         if (self.graph is not None and (self.device_guard or self.loss_threshold >= GUARD_OFF)

@@ -159,7 +159,31 @@ def sampler_d8():
     return rows
 
 
+def resample_op(hp=256, bc=8, rc=32):
+    """rdst_amd/csrc/resample.hip: sample_op_kernel at the benchmark's patch (hp = 256 -> lp = 64): raw[rc][hp | 1], the staged
+    rows of the turned patch, and hs[hp][bc + 1], the horizontal sums of a band's bc LR columns.  Staging walks e = tid over
+    (r, jj) = (e / ncols, e % ncols), transposed variants over (jj, r) = (e / rc, e % rc); the sums are formed by lane = (r = l /
+    bc, oxl = l % bc) reading raw[r][index], index = 4 oxl + k for the sparse tables at ratio 4 and k for the dense one (one
+    address per row: a broadcast); the vertical chains by lane = (oy = l / bc, oxl = l % bc) reading hs[row][oxl], row = 4 oy + k
+    or k."""
+    P, HP = hp | 1, bc + 1
+    return [
+        ("stage write raw[r][jj], lanes along jj", "write_b32", lambda l: 4 * l, "plain and flipped variants"),
+        ("stage write raw[r][jj], lanes along r", "write_b32", lambda l: 4 * ((l % rc) * P + l // rc), "transposed variants"),
+        ("(the same with rows of hp floats)", "write_b32", lambda l: 4 * ((l % rc) * hp + l // rc), "what the odd pitch avoids"),
+        ("HR rows out of raw[r][j]", "read_b32", lambda l: 4 * l, "the chunks the band owns"),
+        ("sums: raw[r][4 oxl + k], ratio 4", "read_b32", lambda l: 4 * ((l // bc) * P + 4 * (l % bc) + 1), "K per sum"),
+        ("sums: raw[r][k], dense", "read_b32", lambda l: 4 * ((l // bc) * P + 1), "K per sum"),
+        ("hs write [r][oxl]", "write_b32", lambda l: 4 * ((l // bc) * HP + l % bc), "1 per sum"),
+        ("chains: hs[4 oy + k][oxl], ratio 4", "read_b32", lambda l: 4 * ((4 * (l // bc) + 1) * HP + l % bc), "K per LR pixel"),
+        ("chains: hs[k][oxl], dense", "read_b32", lambda l: 4 * (HP + l % bc), "K per LR pixel"),
+        ("(hs rows of bc floats: the ratio-4 read)", "read_b32", lambda l: 4 * ((4 * (l // bc) + 1) * bc + l % bc), "what the pad avoids"),
+    ]
+
+
 if __name__ == "__main__":
+    print("== resample.hip sample_op_kernel (raw rows of 257 floats; hs rows of 9 floats)")
+    report(resample_op())
     print("== tiles.hip d8 blocks (rows of 33 floats)")
     report(d8_blocks())
     print("== sampler.hip d8 kernels (the same blocks; hs rows of 10 floats)")
