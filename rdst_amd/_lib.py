@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RDST_HIP_LIB") or os.path.join(_HERE, "librdst_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rdst_hip.h")
 DATA_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rdst_hip_data.h")   # the K-tap degradations (data.py)
+LRC_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rdst_hip_consistency.h")   # LR consistency (loss/consistency.py)
 
 _SCALARS = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
 _FIELD_SCALARS = {**_SCALARS, "int32_t": C.c_int32}
@@ -98,6 +99,8 @@ SIGNATURES, PARAMS, _structs, CONSTANTS = parse_header(_read_header())
 
 # the same of include/rdst_hip_data.h: entry points outside ABI_VERSION's count (a library without them gets raisers)
 DATA_SIGNATURES, DATA_PARAMS, _, _ = parse_header(_read_header(DATA_HEADER_PATH))
+# and of include/rdst_hip_consistency.h, outside the count as well
+LRC_SIGNATURES, LRC_PARAMS, _, _ = parse_header(_read_header(LRC_HEADER_PATH))
 
 PackJob = _structs["rdst_pack_job"]
 LrSchedule = _structs["rdst_lr_schedule"]   # passed by value to rdst_adam_step_dev
@@ -126,7 +129,7 @@ def load() -> C.CDLL:
             f"rdst_amd: {LIB_PATH} is missing. Build it with `python -m rdst_amd.build` "
             "(hipcc --offload-arch=gfx950); there is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **DATA_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **DATA_SIGNATURES, **LRC_SIGNATURES}.items():
         fn = getattr(lib, name, None)
         if fn is None:  # a declared symbol the .so does not export: calling it raises
             setattr(lib, name, _missing(name))

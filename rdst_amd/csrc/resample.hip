@@ -3,7 +3,7 @@
 // bicubic, bicubic followed by cv2's Gaussian blur, Fourier-domain truncation, ...), applied to whole images
 // (rdst_resample_sep) and inside the sampler's one launch (rdst_sample_patches_op).  sampler.hip keeps the 4-tap kernels.
 //
-// Every output is formed by tapk() below, the generalisation of sampler.hip's tap4(): acc = w[0] * v[0] rounded, then one
+// Every output is formed by tapk() (tapk.h), the generalisation of sampler.hip's tap4(): acc = w[0] * v[0] rounded, then one
 // explicit fmaf per tap in ascending order; the horizontal sums of the tap rows first, then the vertical chain over them.
 // A horizontal sum depends on its source row, its output column and the table only, so forming it once and sharing it
 // among the output rows gives the bits of forming it per output pixel: a K = 4 table gives the bits of tap4(), and the
@@ -12,6 +12,7 @@
 // No MFMA, no atomics, no scratch.  Tables are read as int4 / float4 (K % 4 == 0, 16-byte aligned), pixels as dwords with
 // lanes along a source row; every index read from device memory is clamped before it becomes an address.
 #include "common.h"
+#include "tapk.h"
 #include "../../include/rdst_hip_data.h"
 
 namespace {
@@ -21,60 +22,6 @@ constexpr int LDS_BUDGET = 64 * 1024;   // the sampler's budget (the default dyn
 constexpr int BC_MAX = 8;               // LR columns per band
 constexpr int RC_MAX = 32;              // rows of the turned patch per staged chunk
 constexpr int SG = 8;                   // staging loads a thread issues before it stores them
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-// one output value from the 4 * K4 taps of one table row: v(j) is the sample at (unclamped) source index j
-template <class F>
-__device__ __forceinline__ float tapk(const int4* __restrict__ it, const f4* __restrict__ wt, int K4, F v) {
-  int4 j = it[0];
-  f4 w = wt[0];
-  float acc = __fmul_rn(w.x, v(j.x));
-  acc = fmaf(w.y, v(j.y), acc);
-  acc = fmaf(w.z, v(j.z), acc);
-  acc = fmaf(w.w, v(j.w), acc);
-  int q = 1;
-  // long rows, four table entries at a time: their eight loads and sixteen samples are in flight together (a wave forms one
-  // chain per lane and nothing else hides the tables' latency); the order of the sums is the same
-  // (and the next four entries are loaded before the current sixteen taps are summed)
-  int4 jn[4];
-  f4 wn[4];
-  if (q + 4 <= K4) {
-#pragma unroll
-    for (int s = 0; s < 4; ++s) jn[s] = it[q + s], wn[s] = wt[q + s];
-  }
-  for (; q + 4 <= K4; q += 4) {
-    int4 jj[4];
-    f4 ww[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) jj[s] = jn[s], ww[s] = wn[s];
-    if (q + 8 <= K4) {
-#pragma unroll
-      for (int s = 0; s < 4; ++s) jn[s] = it[q + 4 + s], wn[s] = wt[q + 4 + s];
-    }
-    float vv[16];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) vv[4 * s] = v(jj[s].x), vv[4 * s + 1] = v(jj[s].y), vv[4 * s + 2] = v(jj[s].z), vv[4 * s + 3] = v(jj[s].w);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      acc = fmaf(ww[s].x, vv[4 * s], acc);
-      acc = fmaf(ww[s].y, vv[4 * s + 1], acc);
-      acc = fmaf(ww[s].z, vv[4 * s + 2], acc);
-      acc = fmaf(ww[s].w, vv[4 * s + 3], acc);
-    }
-  }
-  for (; q < K4; ++q) {
-    j = it[q];
-    w = wt[q];
-    acc = fmaf(w.x, v(j.x), acc);
-    acc = fmaf(w.y, v(j.y), acc);
-    acc = fmaf(w.z, v(j.z), acc);
-    acc = fmaf(w.w, v(j.w), acc);
-  }
-  return acc;
-}
 
 // ---- rdst_resample_sep: the horizontal sums of every source row, then the vertical chains; one thread per value -------
 __global__ void __launch_bounds__(NT) hsum_kernel(const float* __restrict__ x, float* __restrict__ tmp, int W, int ow, int Kx4,

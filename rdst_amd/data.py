@@ -9,6 +9,8 @@ slices are moved to the GPU once and a batch is cut and degraded where it is con
   * ``bicubic_resize(x, size)``      the resize itself (rdst_resize_bicubic, include/rdst_hip.h);
   * ``resample(x, size, degradation)``  the same under any ``Degradation``: a separable linear operator given as a table of K
                                      taps per output (``operator_table``; rdst_resample_sep, include/rdst_hip_data.h);
+  * ``resample_adjoint(g, size, d)``  its adjoint, the same kernels under the transposed tables (``adjoint_table``);
+                                     ``degrade`` is ``resample`` with that backward, ``operator_norm`` the spectral norm;
   * ``make_test_pair(hr, s)``        ``get_test_pair`` for one scale: what ``SRTester.evaluate`` / ``DPTrainStep.quick_eva`` take;
   * ``DevicePatchSampler``           ``__getitem__``: one HIP launch per batch (rdst_sample_patches), three random integers per
                                      patch drawn on the host, nothing read back; ``DPTrainStep.step_from(sampler)`` trains on it.
@@ -369,6 +371,131 @@ def resample(x: torch.Tensor, size, degradation: Union[str, Degradation] = "cubi
                                          iy.data_ptr(), wy.data_ptr(), ix.shape[1], ix.data_ptr(), wx.data_ptr(), _stream()),
                    "rdst_resample_sep")
     return y[0] if squeeze else y
+
+
+# ---- the adjoints of the K-tap operators --------------------------------------------------------------------------------
+def _operator_matrix(d: Degradation, n_in: int, n_out: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The float64 matrix ``(n_out, n_in)`` of ``operator_table(d, n_in, n_out)`` and the boolean mask of its real taps.  Taps
+    of one row that stand on one sample (the clamped border taps of ``'cubic'``; a padding tap of weight 0.0 on the row's
+    last index) are added in float64; a tap whose weight is exactly 0.0 (three of the four of ``'cubic'`` at an integer ratio
+    and an odd phase, 24 -> 8) is not a real tap."""
+    index, weight = operator_table(d, n_in, n_out)
+    M = np.zeros((index.shape[0], int(n_in)), dtype=np.float64)
+    rows = np.arange(index.shape[0])[:, None]
+    np.add.at(M, (rows, index), weight)
+    support = np.zeros(M.shape, dtype=bool)
+    support[rows, index] = True
+    return M, support & (M != 0)
+
+
+def adjoint_table(kind: Union[str, Degradation], n_in: int, n_out: int, **opts) -> Tuple[np.ndarray, np.ndarray]:
+    """The table of ``A^T`` for ``A = operator_table(kind, n_in, n_out)``: ``(index, weight)``, int32 and float64 ``(n_in,
+    Kt)`` over ``[0, n_out)``, in ``operator_table``'s format: the taps of source sample ``i`` are the outputs that read it, in
+    ascending order, with the weights of the forward table's float64 matrix (the border taps of ``'cubic'`` that meet on one
+    sample are merged by one float64 addition; taps of weight exactly 0.0 are left out); ``Kt`` is the longest row rounded up to a multiple of 4 and a shorter row is
+    padded with weight 0.0 and its last index.  A source sample no output reads (``'cubic'`` 64 -> 8 and 24 -> 8 have such samples) gives a
+    row of weights 0.0 and index 0."""
+    d = Degradation(kind, **opts) if isinstance(kind, str) else Degradation.of(kind)
+    if not isinstance(kind, str) and opts:
+        raise ValueError("adjoint_table: options go with a kind's name, not with a Degradation")
+    M, support = _operator_matrix(d, n_in, n_out)
+    MT, ST = M.T, support.T
+    counts = ST.sum(axis=1)
+    K = max(4, -(-int(counts.max()) // 4) * 4)
+    index = np.zeros((MT.shape[0], K), dtype=np.int32)
+    weight = np.zeros((MT.shape[0], K), dtype=np.float64)
+    for i in range(MT.shape[0]):
+        j = np.flatnonzero(ST[i])
+        if len(j):
+            index[i, :len(j)], index[i, len(j):] = j, j[-1]
+            weight[i, :len(j)] = MT[i, j]
+    return index, weight
+
+
+_OP_NORMS: Dict[tuple, float] = {}
+
+
+def operator_norm(kind: Union[str, Degradation], n_in: int, n_out: int, **opts) -> float:
+    """The spectral norm (largest singular value) of the float64 matrix of ``operator_table(kind, n_in, n_out)``."""
+    d = Degradation(kind, **opts) if isinstance(kind, str) else Degradation.of(kind)
+    if not isinstance(kind, str) and opts:
+        raise ValueError("operator_norm: options go with a kind's name, not with a Degradation")
+    key = (d, int(n_in), int(n_out))
+    if key not in _OP_NORMS:
+        _OP_NORMS[key] = float(np.linalg.norm(_operator_matrix(d, n_in, n_out)[0], 2))
+    return _OP_NORMS[key]
+
+
+_ADJ_TABLES: Dict[tuple, Tuple[torch.Tensor, torch.Tensor]] = {}
+
+
+def _device_adjoint_table(d: Degradation, n_in: int, n_out: int, device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``adjoint_table`` on the device, the weights rounded once to fp32; cached per (kind, options, in, out, device)."""
+    key = (d, int(n_in), int(n_out), device.type, device.index)
+    tab = _ADJ_TABLES.get(key)
+    if tab is None:
+        index, weight = adjoint_table(d, n_in, n_out)
+        tab = (torch.from_numpy(np.ascontiguousarray(index)).to(device),
+               torch.from_numpy(weight.astype(np.float32)).to(device))
+        _ADJ_TABLES[key] = tab
+    return tab
+
+
+def resample_adjoint(g: torch.Tensor, size, degradation: Union[str, Degradation] = "cubic") -> torch.Tensor:
+    """The adjoint of ``resample``: fp32 CUDA ``(N, C, oh, ow)`` (or ``(C, oh, ow)``) -> a new ``(N, C, H, W)`` tensor with
+    ``size = (H, W)``, ``A_y^T . g . A_x`` for the operators ``A`` of ``resample(x, (oh, ow), degradation)`` on an ``H x W``
+    image.  It is rdst_resample_sep under the transposed tables (``adjoint_table``): the horizontal sums over the LR columns
+    first, then the vertical chains, two launches.  Not differentiable."""
+    d = Degradation.of(degradation)
+    if not isinstance(g, torch.Tensor):
+        raise TypeError("resample_adjoint: g must be a torch tensor")
+    _need_gpu("resample_adjoint", g)
+    if g.requires_grad:
+        raise RuntimeError("resample_adjoint is not differentiable: detach the input")
+    if g.dtype != torch.float32:
+        raise TypeError(f"resample_adjoint: g must be float32, got {g.dtype}")
+    squeeze = g.dim() == 3
+    if squeeze:
+        g = g.unsqueeze(0)
+    if g.dim() != 4:
+        raise ValueError("resample_adjoint: g must have 3 or 4 dimensions")
+    H, W = _pair(size)
+    N, C, oh, ow = g.shape
+    if min(N, C, oh, ow) <= 0 or H <= 0 or W <= 0:
+        raise ValueError(f"resample_adjoint: sizes must be positive, got {tuple(g.shape)} -> {(H, W)}")
+    g = g.contiguous()
+    lib = _lib.load()
+    with torch.cuda.device(g.device):
+        iy, wy = _device_adjoint_table(d, H, oh, g.device)
+        ix, wx = _device_adjoint_table(d, W, ow, g.device)
+        y = torch.empty(N, C, H, W, dtype=torch.float32, device=g.device)
+        tmp = torch.empty(N * C * oh * W, dtype=torch.float32, device=g.device)
+        _lib.check(lib.rdst_resample_sep(g.data_ptr(), y.data_ptr(), tmp.data_ptr(), N, C, oh, ow, H, W, iy.shape[1],
+                                         iy.data_ptr(), wy.data_ptr(), ix.shape[1], ix.data_ptr(), wx.data_ptr(), _stream()),
+                   "rdst_resample_sep")
+    return y[0] if squeeze else y
+
+
+class _Degrade(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, size, d):
+        ctx.hw, ctx.d = tuple(x.shape[-2:]), d
+        return resample(x.detach(), size, d)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        return resample_adjoint(grad.contiguous(), ctx.hw, ctx.d), None, None
+
+
+def degrade(x: torch.Tensor, size, degradation: Union[str, Degradation] = "cubic") -> torch.Tensor:
+    """``resample`` that takes part in autograd: the forward has ``resample``'s bits, the backward is ``resample_adjoint`` of
+    the incoming gradient.  It cannot be differentiated twice."""
+    d = Degradation.of(degradation)
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("degrade: x must be a torch tensor")
+    _need_gpu("degrade", x)
+    return _Degrade.apply(x, _pair(size), d)
 
 
 def make_test_pair(hr: torch.Tensor, s: float, degradation: Union[None, str, Degradation] = None):

@@ -3,6 +3,9 @@ components that sit on this repository's path: 'L1' / 'L2' / 'MSE' (``RecLoss``,
 (``SegUNet_F``, loss/seg_unet.py).  VGG / GAN components are outside SURVEY.md section 8 and raise.  'SSIM' (``SSIMLoss``,
 ssim.py) is this repository's own addition: ``1 - SSIM`` from one HIP kernel, e.g. ``{'L1': 0.16, 'SSIM': 0.84}``; optional
 ``paras.ssim_window`` ('uniform' / 'gaussian'), ``ssim_win_size``, ``ssim_sigma`` and ``ssim_data_range`` configure it.
+'LRC' (``LRConsistencyLoss``, consistency.py) is the other: the L1 / L2 distance of the DEGRADED prediction to the degraded
+target, e.g. ``{'L1': 1, 'LRC': 0.1}``; optional ``paras.lrc_degradation`` (default ``Degradation.from_paras(paras)``),
+``lrc_norm`` ('L1' / 'L2', default 'L1') and ``lrc_scale`` (default ``paras.sr_scale``) configure it.
 
     loss, repo = SRLoss(paras)(pred, gt)       # sum_n scalars[state][n] * component_n(pred, gt)
 
@@ -20,6 +23,8 @@ from typing import Dict
 import torch
 import torch.nn.functional as F
 
+from ..data import Degradation
+from .consistency import LRConsistencyLoss
 from .seg_unet import SegUNet_F
 from .ssim import SSIMLoss
 
@@ -87,11 +92,16 @@ class SRLoss(object):
             elif l in ["SSIM"]:
                 f = SSIMLoss(window=getattr(paras, "ssim_window", "uniform"), win_size=getattr(paras, "ssim_win_size", None),
                              sigma=getattr(paras, "ssim_sigma", 1.5), data_range=getattr(paras, "ssim_data_range", 1.0))
+            elif l in ["LRC"]:
+                d = getattr(paras, "lrc_degradation", None)
+                f = LRConsistencyLoss(degradation=Degradation.from_paras(paras) if d is None else d,
+                                      scale=getattr(paras, "lrc_scale", None) or paras.sr_scale,
+                                      norm=getattr(paras, "lrc_norm", "L1"))
             else:
                 raise NotImplementedError(
                     "rdst_amd.loss.SRLoss: loss component {!r} is outside this repository's scope (SURVEY.md section 8: "
-                    "L1 / L2 / MSE and UNet-F are on the path, SSIM is this repository's own; VGG and GAN losses are "
-                    "not)".format(l))
+                    "L1 / L2 / MSE and UNet-F are on the path, SSIM and LRC are this repository's own; VGG and GAN losses "
+                    "are not)".format(l))
             self.loss_components += f.loss_names
             self.loss_functions[l] = f
 

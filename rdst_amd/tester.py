@@ -52,12 +52,19 @@ class SRTester:
     EDSR / RCAN / SwinIR, per tile.  A network call carries ``tile_batch / 8`` tiles, each under its eight flips and
     transposes (``tiling.unfold_tiles_d8``, slot ``8 t + k``); the eight outputs are transformed back and averaged in fp32
     (``tiling.merge_tiles_d8``) straight into the tile buffer, which is folded as before.  Tiles are square, so the tile batch
-    and the captured graph are the ones of the plain path: 8x the network calls, one unfold and one merge launch per call."""
+    and the captured graph are the ones of the plain path: 8x the network calls, one unfold and one merge launch per call.
+
+    ``back_project=k`` (an integer scale only): ``k`` Landweber steps ``P <- P - tau A^T(A P - lr)`` on every chunk of whole SR
+    slices against its LR slices, on both paths, so the output agrees with the slices that were measured; ``A`` is
+    ``degradation`` (default ``'cubic'``; ``data.operator_table(d, h s, h)`` along each axis) and ``tau`` is ``bp_step`` or
+    ``1 / (|A_y|^2 |A_x|^2)`` (``data.operator_norm``; the iteration contracts for ``tau < 2 / |A|^4``).  The steps run in fp32, so with
+    ``back_project > 0`` the result is fp32 whatever dtype the network returns; ``0`` takes no step and keeps the network's dtype."""
 
     def __init__(self, net: torch.nn.Module, batch_size: int = 16, sr_scale: Optional[float] = None,
                  metrics: str = "psnr ssim", compute_dtype: Optional[torch.dtype] = None, *, tile: Optional[int] = None,
                  tile_stride: Optional[int] = None, tile_batch: int = 32, pad_mode: str = "zero", graph: bool = False,
-                 tile_buffer_bytes: int = 1 << 30, self_ensemble: bool = False):
+                 tile_buffer_bytes: int = 1 << 30, self_ensemble: bool = False, back_project: int = 0, degradation=None,
+                 bp_step: Optional[float] = None):
         self.net = net
         self.batch_size = int(batch_size)
         self.sr_scale = float(sr_scale if sr_scale is not None else getattr(net, "sr_scale", getattr(net, "upscale", 1)))
@@ -74,6 +81,20 @@ class SRTester:
         if self.self_ensemble and self.tile is None:
             raise ValueError("SRTester: self_ensemble=True needs the tiled path (tile=...); a square slice that is a multiple of "
                              "the window size can be run as one tile (tile=H, tile_stride=H)")
+        # back-projection
+        if isinstance(back_project, bool) or int(back_project) != back_project or back_project < 0:
+            raise ValueError(f"SRTester: back_project={back_project!r} must be a non-negative number of steps")
+        self.back_project = int(back_project)
+        self.degradation = self.bp_step = None
+        if self.back_project:
+            from .data import Degradation
+            self.degradation = Degradation.of("cubic" if degradation is None else degradation)
+            if self.sr_scale != int(self.sr_scale) or self.sr_scale < 1:
+                raise ValueError(f"SRTester: back-projection needs an integer scale, got {self.sr_scale}")
+            if bp_step is not None:
+                if not (math.isfinite(float(bp_step)) and float(bp_step) > 0):
+                    raise ValueError(f"SRTester: bp_step={bp_step!r} must be positive and finite")
+                self.bp_step = float(bp_step)
         self.graph = None
         self.graph_captures = self.graph_replays = 0
         self._static_in = self._static_out = self._graph_plan = self._graph_sig = None
@@ -104,8 +125,38 @@ class SRTester:
         dev = next(self.net.parameters()).device
         if self.tile is not None:
             return self._tiled(lr_img, dev)
-        rec = [self.net(p.to(dev)) for p in lr_img.split(self.batch_size * 4)]
+        if self.back_project:
+            rec = []
+            for p in lr_img.split(self.batch_size * 4):
+                p = p.to(dev)
+                rec.append(self._back_projected(self.net(p), p))
+        else:
+            rec = [self.net(p.to(dev)) for p in lr_img.split(self.batch_size * 4)]
         return torch.cat(rec, dim=0)
+
+    # ---- back-projection ---------------------------------------------------------------------------------------------
+    def _back_projected(self, P: torch.Tensor, lr: torch.Tensor, own: bool = False) -> torch.Tensor:
+        """``back_project`` Landweber steps ``P <- P - tau A^T(A P - lr)`` on the SR slices ``P`` (N, C, h s, w s) of the LR
+        slices ``lr`` (N, C, h, w): two launches per step, the residual of the degraded slices (rdst_lrc_residual) and the
+        adjoint with ``P`` as its base, in place (rdst_lrc_adjoint).  ``tau`` is ``bp_step`` or ``1 / (|A_y|^2 |A_x|^2)``."""
+        from .data import operator_norm
+        from .loss.consistency import lrc_adjoint, lrc_residual
+        s, d = int(self.sr_scale), self.degradation
+        h, w = lr.shape[-2:]
+        if tuple(P.shape[-2:]) != (h * s, w * s) or P.shape[:2] != lr.shape[:2]:
+            raise RuntimeError(f"SRTester.inference: back-projection expects {(h * s, w * s)} SR slices of {(h, w)} LR slices, "
+                               f"the network gave {tuple(P.shape)} for {tuple(lr.shape)}")
+        tau = self.bp_step
+        if tau is None:
+            tau = 1.0 / (operator_norm(d, h * s, h) ** 2 * operator_norm(d, w * s, w) ** 2)
+        out = P.detach().to(torch.float32).contiguous()
+        if out.data_ptr() == P.data_ptr() and not own:
+            out = out.clone()           # the network's output may be a buffer it keeps
+        lr = lr.detach().to(torch.float32).contiguous()
+        for _ in range(self.back_project):
+            resid, _, _ = lrc_residual(out, lr, d)
+            lrc_adjoint(resid, (h * s, w * s), d, scale=-tau, base=out, out=out)
+        return out
 
     # ---- the tiled path ----------------------------------------------------------------------------------------------
     def _tile_plan(self, h: int, w: int):
@@ -149,7 +200,8 @@ class SRTester:
                             merge_tiles_d8(y[:E * m] if y.dtype == torch.float32 else y[:E * m].float(), out=tiles[f:f + m])
                         else:
                             tiles[f:f + m].copy_(y[:m])
-                    rec.append(fold_tiles(tiles, plan, n))
+                    sr = fold_tiles(tiles, plan, n)
+                    rec.append(self._back_projected(sr, x, own=True) if self.back_project else sr)
             finally:
                 self._plan = ops.pack_plan_of(self.net)
         return rec[0] if len(rec) == 1 else torch.cat(rec, dim=0)
