@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("RDST_HIP_LIB") or os.path.join(_HERE, "librdst_hip.so
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rdst_hip.h")
 DATA_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rdst_hip_data.h")   # the K-tap degradations (data.py)
 LRC_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rdst_hip_consistency.h")   # LR consistency (loss/consistency.py)
+MSSSIM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rdst_hip_msssim.h")   # MS-SSIM (loss/msssim.py, metrics.py)
 
 _SCALARS = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
 _FIELD_SCALARS = {**_SCALARS, "int32_t": C.c_int32}
@@ -101,6 +102,8 @@ SIGNATURES, PARAMS, _structs, CONSTANTS = parse_header(_read_header())
 DATA_SIGNATURES, DATA_PARAMS, _, _ = parse_header(_read_header(DATA_HEADER_PATH))
 # and of include/rdst_hip_consistency.h, outside the count as well
 LRC_SIGNATURES, LRC_PARAMS, _, _ = parse_header(_read_header(LRC_HEADER_PATH))
+# and of include/rdst_hip_msssim.h, outside the count as well
+MSSSIM_SIGNATURES, MSSSIM_PARAMS, _, _ = parse_header(_read_header(MSSSIM_HEADER_PATH))
 
 PackJob = _structs["rdst_pack_job"]
 LrSchedule = _structs["rdst_lr_schedule"]   # passed by value to rdst_adam_step_dev
@@ -129,7 +132,7 @@ def load() -> C.CDLL:
             f"rdst_amd: {LIB_PATH} is missing. Build it with `python -m rdst_amd.build` "
             "(hipcc --offload-arch=gfx950); there is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **DATA_SIGNATURES, **LRC_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **DATA_SIGNATURES, **LRC_SIGNATURES, **MSSSIM_SIGNATURES}.items():
         fn = getattr(lib, name, None)
         if fn is None:  # a declared symbol the .so does not export: calling it raises
             setattr(lib, name, _missing(name))

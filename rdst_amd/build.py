@@ -37,7 +37,8 @@ def build(force: bool = False, verbose: bool = True, debug: bool = False) -> str
     os.makedirs(OBJ, exist_ok=True)
     srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hdrs += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("rdst_hip.h", "rdst_hip_data.h", "rdst_hip_consistency.h")]
+    hdrs += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("rdst_hip.h", "rdst_hip_data.h", "rdst_hip_consistency.h",
+                                                                            "rdst_hip_msssim.h")]
     jobs = []
     objs = []
     for s in srcs:

@@ -6,6 +6,10 @@ ssim.py) is this repository's own addition: ``1 - SSIM`` from one HIP kernel, e.
 'LRC' (``LRConsistencyLoss``, consistency.py) is the other: the L1 / L2 distance of the DEGRADED prediction to the degraded
 target, e.g. ``{'L1': 1, 'LRC': 0.1}``; optional ``paras.lrc_degradation`` (default ``Degradation.from_paras(paras)``),
 ``lrc_norm`` ('L1' / 'L2', default 'L1') and ``lrc_scale`` (default ``paras.sr_scale``) configure it.
+'MSSSIM' (``MSSSIMLoss``, msssim.py) is the multi-scale form of 'SSIM', the one Zhao et al.'s 0.16 / 0.84 mix was defined
+with: ``{'L1': 0.16, 'MSSSIM': 0.84}``; optional ``paras.msssim_levels`` (default 5; 96-pixel patches hold 4 at 11 taps),
+``msssim_weights``, ``msssim_window`` (default 'gaussian'), ``msssim_win_size``, ``msssim_sigma`` and ``msssim_data_range``
+configure it.  Patches too small for the levels raise at the first step; the levels are never reduced silently.
 
     loss, repo = SRLoss(paras)(pred, gt)       # sum_n scalars[state][n] * component_n(pred, gt)
 
@@ -26,6 +30,7 @@ import torch.nn.functional as F
 from ..data import Degradation
 from .consistency import LRConsistencyLoss
 from .seg_unet import SegUNet_F
+from .msssim import MSSSIMLoss
 from .ssim import SSIMLoss
 
 
@@ -92,6 +97,11 @@ class SRLoss(object):
             elif l in ["SSIM"]:
                 f = SSIMLoss(window=getattr(paras, "ssim_window", "uniform"), win_size=getattr(paras, "ssim_win_size", None),
                              sigma=getattr(paras, "ssim_sigma", 1.5), data_range=getattr(paras, "ssim_data_range", 1.0))
+            elif l in ["MSSSIM"]:
+                f = MSSSIMLoss(levels=getattr(paras, "msssim_levels", 5), weights=getattr(paras, "msssim_weights", None),
+                               window=getattr(paras, "msssim_window", "gaussian"),
+                               win_size=getattr(paras, "msssim_win_size", None), sigma=getattr(paras, "msssim_sigma", 1.5),
+                               data_range=getattr(paras, "msssim_data_range", 1.0))
             elif l in ["LRC"]:
                 d = getattr(paras, "lrc_degradation", None)
                 f = LRConsistencyLoss(degradation=Degradation.from_paras(paras) if d is None else d,
@@ -100,8 +110,8 @@ class SRLoss(object):
             else:
                 raise NotImplementedError(
                     "rdst_amd.loss.SRLoss: loss component {!r} is outside this repository's scope (SURVEY.md section 8: "
-                    "L1 / L2 / MSE and UNet-F are on the path, SSIM and LRC are this repository's own; VGG and GAN losses "
-                    "are not)".format(l))
+                    "L1 / L2 / MSE and UNet-F are on the path, SSIM and LRC are this repository's own, as is MSSSIM; VGG and GAN "
+                    "losses are not)".format(l))
             self.loss_components += f.loss_names
             self.loss_functions[l] = f
 
