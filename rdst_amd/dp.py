@@ -31,6 +31,16 @@ def take_grad_view(param: torch.Tensor):
     return _OFFERED.pop(param.data_ptr(), None) if _OFFERED else None
 
 
+def flat_views(flat: torch.Tensor, like: Iterable[torch.Tensor]):
+    """The views of the 1-D buffer ``flat`` that lay the tensors of ``like`` end to end: one per tensor, in order, with that
+    tensor's shape, each starting where the one before ended.  They alias ``flat``; nothing is copied."""
+    off = 0
+    for t in like:
+        k = t.numel()
+        yield flat[off:off + k].view_as(t)
+        off += k
+
+
 class FlatGradBucket:
     """Owns one contiguous fp32 buffer; ``p.grad`` of every trainable parameter is a view of it.
 
@@ -48,12 +58,10 @@ class FlatGradBucket:
         dev = self.params[0].device
         n = sum(p.numel() for p in self.params)
         self.flat = torch.zeros(n, dtype=torch.float32, device=dev)
-        off = 0
-        for p in self.params:
+        for p, view in zip(self.params, flat_views(self.flat, self.params)):
             if p.dtype != torch.float32 or p.device != dev:
                 raise ValueError("FlatGradBucket: parameters must be fp32 on one device")
-            p.grad = self.flat[off:off + p.numel()].view_as(p)
-            off += p.numel()
+            p.grad = view
 
     @property
     def nbytes(self) -> int:
@@ -69,11 +77,9 @@ class FlatGradBucket:
         a weight-gradient kernel then writes straight into the bucket and ``gather()`` has nothing to copy."""
         global _OFFERED
         offered = {}
-        off = 0
-        for p in self.params:
+        for p, view in zip(self.params, flat_views(self.flat, self.params)):
             p.grad = None
-            offered[p.data_ptr()] = self.flat[off:off + p.numel()].view_as(p)
-            off += p.numel()
+            offered[p.data_ptr()] = view
         _OFFERED = offered
 
     def gather(self) -> None:
@@ -81,17 +87,13 @@ class FlatGradBucket:
         zeros) and make ``p.grad`` the bucket views again."""
         global _OFFERED
         _OFFERED = {}
-        base = self.flat.data_ptr()
-        off = 0
-        for p in self.params:
-            view = self.flat[off:off + p.numel()].view_as(p)
+        for p, view in zip(self.params, flat_views(self.flat, self.params)):
             g = p.grad
             if g is None:
                 view.zero_()
-            elif g.data_ptr() != base + 4 * off:     # not written in place by the op: copy it in
+            elif g.data_ptr() != view.data_ptr():     # not written in place by the op: copy it in
                 view.copy_(g)
             p.grad = view
-            off += p.numel()
 
     def check_views(self) -> bool:
         """True while every p.grad still aliases the bucket (zero_grad(set_to_none=True) breaks it)."""
@@ -128,7 +130,5 @@ def broadcast_parameters(module: torch.nn.Module, src: int = 0, group=None) -> N
     for dt, ts in by_dtype.items():
         flat = torch.cat([t.reshape(-1) for t in ts])
         dist.broadcast(flat, src=src, group=group)
-        off = 0
-        for t in ts:
-            t.copy_(flat[off:off + t.numel()].view_as(t))
-            off += t.numel()
+        for t, view in zip(ts, flat_views(flat, ts)):
+            t.copy_(view)

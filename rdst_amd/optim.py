@@ -24,13 +24,16 @@ from __future__ import annotations
 
 import bisect
 import contextlib
+import ctypes as C
 import math
 from typing import Iterable, Optional, Sequence
 
 import torch
 
 from . import _lib
-from .dp import FlatGradBucket
+from .dp import FlatGradBucket, flat_views
+
+_TORCH_DTYPE = {C.c_int64: torch.int64, C.c_int32: torch.int32, C.c_float: torch.float32, C.c_double: torch.float64}
 
 
 def multistep_table(base_lr: float, milestones: Sequence[int], gamma: float) -> list:
@@ -97,13 +100,10 @@ class FlatAdam(torch.optim.Optimizer):
             nbytes = int(_lib.load().rdst_step_guard_workspace(n)) if dev.type == "cuda" else 0
             self._workspace = torch.empty(max(nbytes, 16) // 8, dtype=torch.float64, device=dev)
             self._push_state(0)
-        off = 0
         with torch.no_grad():
-            for p in params:
-                k = p.numel()
-                self.flat_param[off:off + k].copy_(p.data.reshape(-1))
-                p.data = self.flat_param[off:off + k].view_as(p)  # the module now computes from the flat buffer
-                off += k
+            for p, view in zip(params, flat_views(self.flat_param, params)):
+                view.copy_(p.data)
+                p.data = view  # the module now computes from the flat buffer
         # the weight EMA: one more flat buffer, a copy of the parameters as they are now; nothing without ema_decay
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.ema_warmup = bool(ema_warmup)
@@ -111,17 +111,17 @@ class FlatAdam(torch.optim.Optimizer):
         self.ema = self.flat_param.clone() if self.ema_decay is not None else None
         self._point_state()
 
+    def _need_gpu(self, where: str, what: str) -> None:
+        if not self.flat_param.is_cuda:
+            raise RuntimeError(f"rdst_amd.optim.FlatAdam.{where}: the {what} is a HIP kernel; there is no CPU fallback")
+
     def _point_state(self) -> None:
         # ONE host-side step counter shared by all 750 per-parameter states (torch.optim.Adam's layout wants a
         # "step" entry per parameter; they are always equal here): a step() updates it once, not 750 times
         self._step_t = torch.tensor(float(self._steps))
-        off = 0
-        for p in self.param_groups[0]["params"]:
-            k = p.numel()
-            self.state[p] = {"step": self._step_t,
-                             "exp_avg": self.exp_avg[off:off + k].view_as(p),
-                             "exp_avg_sq": self.exp_avg_sq[off:off + k].view_as(p)}
-            off += k
+        params = self.param_groups[0]["params"]
+        for p, m, v in zip(params, flat_views(self.exp_avg, params), flat_views(self.exp_avg_sq, params)):
+            self.state[p] = {"step": self._step_t, "exp_avg": m, "exp_avg_sq": v}
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -129,8 +129,7 @@ class FlatAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        if not self.flat_param.is_cuda:
-            raise RuntimeError("rdst_amd.optim.FlatAdam.step: the fused update is a HIP kernel; there is no CPU fallback")
+        self._need_gpu("step", "fused update")
         if self.ema_active:
             raise RuntimeError("FlatAdam.step: the parameters hold the averaged weights (swap_ema / ema_scope is active); "
                                "the network must not train on them")
@@ -146,18 +145,19 @@ class FlatAdam(torch.optim.Optimizer):
         hyper = [float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"])]
         ema_args = [self.ema_decay, int(self.ema_warmup)] if ema else []
         n, stream = self.flat_param.numel(), torch.cuda.current_stream().cuda_stream
+        # the four entry points differ in where rate and count come from: (lr, ..., step) from the host, or (schedule, ..., state)
         if self.device_state:
             if not self._guard_pending:     # no guard() before this step: it is kept
                 self.guard(None, 0.0)
             self._guard_pending = False
-            name = "rdst_adam_step_dev_ema" if ema else "rdst_adam_step_dev"
-            _lib.check(getattr(lib, name)(*bufs, n, self._c_schedule(), *hyper, *ema_args, self._dev_state.data_ptr(), stream),
-                       name)
-            return loss
-        self._steps += 1
-        name = "rdst_adam_step_ema" if ema else "rdst_adam_step"
-        _lib.check(getattr(lib, name)(*bufs, n, float(g["lr"]), *hyper, self._steps, *ema_args, stream), name)
-        self._step_t.fill_(float(self._steps))
+            rate, count = self._c_schedule(), [*ema_args, self._dev_state.data_ptr()]
+        else:
+            self._steps += 1
+            rate, count = float(g["lr"]), [self._steps, *ema_args]
+        name = "rdst_adam_step" + ("_dev" if self.device_state else "") + ("_ema" if ema else "")
+        _lib.check(getattr(lib, name)(*bufs, n, rate, *hyper, *count, stream), name)
+        if not self.device_state:
+            self._step_t.fill_(float(self._steps))
         return loss
 
     def zero_grad(self, set_to_none: bool = False) -> None:  # noqa: D401 - keeps p.grad aliased to the bucket
@@ -182,8 +182,7 @@ class FlatAdam(torch.optim.Optimizer):
         of the network is a view of ``flat_param``, so the network computes from the averaged weights until the next call;
         no address moves, so pack plans and captured graphs (whose pack refresh is one of their nodes) stay valid."""
         self._need_ema("swap_ema")
-        if not self.flat_param.is_cuda:
-            raise RuntimeError("rdst_amd.optim.FlatAdam.swap_ema: the exchange is a HIP kernel; there is no CPU fallback")
+        self._need_gpu("swap_ema", "exchange")
         _lib.check(_lib.load().rdst_swap_f32(self.flat_param.data_ptr(), self.ema.data_ptr(), self.flat_param.numel(),
                                              torch.cuda.current_stream().cuda_stream), "rdst_swap_f32")
         self.ema_active = not self.ema_active
@@ -202,12 +201,7 @@ class FlatAdam(torch.optim.Optimizer):
         """Per-parameter views of ``ema``, in parameter order.  Inside ``ema_scope()`` the buffers are exchanged: these
         views then show the live weights and the parameters the averaged ones."""
         self._need_ema("ema_views")
-        out, off = [], 0
-        for p in self.param_groups[0]["params"]:
-            k = p.numel()
-            out.append(self.ema[off:off + k].view_as(p))
-            off += k
-        return out
+        return list(flat_views(self.ema, self.param_groups[0]["params"]))
 
     # ---- device-resident step state (device_state=True) ------------------------------------------------------------
     def _need_device_state(self, what: str) -> None:
@@ -257,8 +251,7 @@ class FlatAdam(torch.optim.Optimizer):
         self._need_device_state("guard")
         if self.ema_active:
             raise RuntimeError("FlatAdam.guard: the parameters hold the averaged weights (swap_ema / ema_scope is active)")
-        if not self.flat_param.is_cuda:
-            raise RuntimeError("rdst_amd.optim.FlatAdam.guard: the guard is a HIP kernel; there is no CPU fallback")
+        self._need_gpu("guard", "guard")
         if loss is not None and (loss.dtype != torch.float32 or loss.device != self.flat_param.device or loss.numel() != 1):
             raise ValueError("FlatAdam.guard: loss must be one fp32 element on the optimizer's device")
         if peer_skip is not None and (peer_skip.dtype != torch.int32 or peer_skip.device != self.flat_param.device
@@ -277,9 +270,8 @@ class FlatAdam(torch.optim.Optimizer):
         """The ONE place that reads the step state back (one copy): brings ``_steps``, the shared "step" tensor,
         ``param_groups[0]["lr"]`` and an attached scheduler to where ``kept`` applied updates leave them."""
         self._need_device_state("sync_host")
-        h = self._dev_state.cpu()
-        i32, f32, f64 = h.view(torch.int32), h.view(torch.float32), h.view(torch.float64)
-        kept, sumsq = int(h[0]), float(f64[4])
+        st = self.host_state()
+        kept, sumsq = st.kept, st.last_sumsq
         self._steps = kept
         self._step_t.fill_(float(kept))
         if self._lr_table is not None:
@@ -288,17 +280,25 @@ class FlatAdam(torch.optim.Optimizer):
             if self.scheduler is not None:
                 for k, v in fields.items():
                     setattr(self.scheduler, k, v)
-        return {"kept": kept, "skipped": int(h[1]), "last_keep": int(i32[4]), "last_reason": int(i32[5]),
+        return {"kept": kept, "skipped": st.skipped, "last_keep": st.last_keep, "last_reason": st.last_reason,
                 "last_grad_norm": None if sumsq == -1.0 else math.sqrt(sumsq) if sumsq < math.inf else sumsq,
-                "last_clip": float(f32[6]), "last_lr": float(f32[7])}
+                "last_clip": st.last_clip, "last_lr": st.last_lr}
+
+    def host_state(self) -> "_lib.StepState":
+        """A host copy of the rdst_step_state, read by field name (one device-to-host copy)."""
+        self._need_device_state("host_state")
+        return _lib.StepState.from_buffer_copy(self._dev_state.cpu().numpy().tobytes())
+
+    def state_field(self, name: str) -> torch.Tensor:
+        """The 0-dim view of one field of the rdst_step_state where it lives (no copy, nothing read back)."""
+        self._need_device_state("state_field")
+        f = getattr(_lib.StepState, name)
+        dtype = _TORCH_DTYPE[dict(_lib.StepState._fields_)[name]]
+        return self._dev_state.view(torch.uint8)[f.offset:f.offset + f.size].view(dtype)[0]
 
     def _push_state(self, kept: int) -> None:
-        h = torch.zeros(_lib.STEP_STATE_BYTES // 8, dtype=torch.int64)
-        h[0] = int(kept)
-        h.view(torch.int32)[4] = 1
-        h.view(torch.float32)[6] = 1.0
-        h.view(torch.float64)[4] = -1.0
-        self._dev_state.copy_(h)
+        st = _lib.StepState(kept=int(kept), last_keep=1, last_clip=1.0, last_sumsq=-1.0)     # the rest 0
+        self._dev_state.copy_(torch.frombuffer(bytearray(st), dtype=torch.int64))
         self._guard_pending = False
 
     def state_dict(self):
@@ -311,20 +311,18 @@ class FlatAdam(torch.optim.Optimizer):
     def load_state_dict(self, state_dict) -> None:
         """Accepts a torch.optim.Adam state dict (same layout as ours) and re-flattens it."""
         super().load_state_dict(state_dict)
-        off = 0
         steps = 0
+        params = self.param_groups[0]["params"]
         with torch.no_grad():
-            for p in self.param_groups[0]["params"]:
-                k = p.numel()
+            for p, m, v in zip(params, flat_views(self.exp_avg, params), flat_views(self.exp_avg_sq, params)):
                 st = self.state.get(p, {})
                 if "exp_avg" in st:
-                    self.exp_avg[off:off + k].copy_(st["exp_avg"].reshape(-1))
-                    self.exp_avg_sq[off:off + k].copy_(st["exp_avg_sq"].reshape(-1))
+                    m.copy_(st["exp_avg"].reshape(m.shape))
+                    v.copy_(st["exp_avg_sq"].reshape(v.shape))
                     steps = max(steps, int(float(st["step"])))
                 else:
-                    self.exp_avg[off:off + k].zero_()
-                    self.exp_avg_sq[off:off + k].zero_()
-                off += k
+                    m.zero_()
+                    v.zero_()
         self._steps = steps
         self._point_state()
         if self.device_state:

@@ -139,7 +139,7 @@ class DPTrainStep:
         rep = self.last_report
         # device_guard: the step's decision (rdst_step_state.last_keep) is parked next to the loss; _flush_records drops
         # the steps that were skipped, which the reference never records (trans_sr_trainer.py:162-167)
-        keep = self.optimizer._dev_state.view(torch.int32)[4].clone() if self.device_guard else None
+        keep = self.optimizer.state_field("last_keep").clone() if self.device_guard else None
         if isinstance(rep, dict) and rep:
             for n in self.training_loss_names:
                 if n in rep:

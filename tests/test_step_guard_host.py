@@ -101,3 +101,58 @@ def test_sync_host_sets_the_scheduler_fields(kept):
     assert opt._steps == kept and float(opt.state[opt.param_groups[0]["params"][0]]["step"]) == float(kept)
     sd_a, sd_b = copy.deepcopy(sch.state_dict()), ref.state_dict()
     assert sd_a["last_epoch"] == sd_b["last_epoch"] and sd_a["_step_count"] == sd_b["_step_count"]
+
+
+STATE_FORMAT = "<qqiiffdq"          # rdst_step_state as include/rdst_hip.h lays it out
+STATE_FIELDS = ("kept", "skipped", "last_keep", "last_reason", "last_clip", "last_lr", "last_sumsq", "reserved")
+
+
+def test_step_state_is_read_by_field_name():
+    import struct
+    from rdst_amd import _lib
+    from rdst_amd.optim import FlatAdam
+    values = (7, 3, 1, 5, 0.375, 2.5e-4, 1234.5625, -9)            # distinct, each exact in its field's type
+    packed = struct.pack(STATE_FORMAT, *values)
+    assert len(packed) == _lib.STEP_STATE_BYTES == 48
+    opt = FlatAdam(_params(), lr=1e-3, device_state=True)
+    opt._dev_state.copy_(torch.frombuffer(bytearray(packed), dtype=torch.int64))
+    st = opt.host_state()
+    assert tuple(getattr(st, n) for n in STATE_FIELDS) == struct.unpack(STATE_FORMAT, packed)
+    assert struct.unpack(STATE_FORMAT, packed) == (7, 3, 1, 5, 0.375, float(np.float32(2.5e-4)), 1234.5625, -9)
+    # the view of a field where the state lives: the same value, aliasing the state (what the trainer parks per step)
+    for n, want in zip(STATE_FIELDS, struct.unpack(STATE_FORMAT, packed)):
+        view = opt.state_field(n)
+        assert view.dim() == 0 and view.item() == want, n
+        assert view.data_ptr() == opt._dev_state.data_ptr() + getattr(_lib.StepState, n).offset
+    assert opt.state_field("last_keep").dtype == torch.int32
+    got = opt.sync_host()
+    assert got == {"kept": 7, "skipped": 3, "last_keep": 1, "last_reason": 5, "last_grad_norm": 1234.5625 ** 0.5,
+                   "last_clip": 0.375, "last_lr": float(np.float32(2.5e-4))}
+    with pytest.raises(RuntimeError):
+        FlatAdam(_params(), lr=1e-3).state_field("last_keep")      # needs device_state=True
+
+
+@pytest.mark.parametrize("k", [0, 5, 2 ** 40 + 1])
+def test_push_state_writes_exactly_these_bytes(k):
+    import struct
+    from rdst_amd.optim import FlatAdam
+    opt = FlatAdam(_params(), lr=1e-3, device_state=True)
+    opt._dev_state.fill_(-1)
+    opt._guard_pending = True
+    opt._push_state(k)
+    assert opt._dev_state.dtype == torch.int64
+    assert opt._dev_state.numpy().tobytes() == struct.pack(STATE_FORMAT, k, 0, 1, 0, 1.0, 0.0, -1.0, 0)
+    assert opt._guard_pending is False
+
+
+def test_flat_views_tile_the_buffer_in_order():
+    from rdst_amd.dp import flat_views
+    like = [torch.empty(2, 3), torch.empty(5), torch.empty(())]    # the last one is 0-dim: one element
+    flat = torch.arange(12, dtype=torch.float32)
+    views = list(flat_views(flat, like))
+    assert [v.shape for v in views] == [t.shape for t in like]
+    assert torch.equal(torch.cat([v.reshape(-1) for v in views]), flat)          # in order, nothing left over
+    assert [v.data_ptr() - flat.data_ptr() for v in views] == [0, 24, 44]
+    for i, v in enumerate(views):                                                # they alias the buffer
+        v.fill_(-float(i + 1))
+    assert flat.tolist() == [-1.0] * 6 + [-2.0] * 5 + [-3.0]
