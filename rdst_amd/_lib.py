@@ -18,6 +18,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rdst_hip.h")
 DATA_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rdst_hip_data.h")   # the K-tap degradations (data.py)
 LRC_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rdst_hip_consistency.h")   # LR consistency (loss/consistency.py)
 MSSSIM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rdst_hip_msssim.h")   # MS-SSIM (loss/msssim.py, metrics.py)
+NOISE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rdst_hip_noise.h")   # the noise term (data.py)
 
 _SCALARS = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
 _FIELD_SCALARS = {**_SCALARS, "int32_t": C.c_int32}
@@ -104,6 +105,9 @@ DATA_SIGNATURES, DATA_PARAMS, _, _ = parse_header(_read_header(DATA_HEADER_PATH)
 LRC_SIGNATURES, LRC_PARAMS, _, _ = parse_header(_read_header(LRC_HEADER_PATH))
 # and of include/rdst_hip_msssim.h, outside the count as well
 MSSSIM_SIGNATURES, MSSSIM_PARAMS, _, _ = parse_header(_read_header(MSSSIM_HEADER_PATH))
+# and of include/rdst_hip_noise.h, outside the count as well; its two model numbers are its own constants
+NOISE_SIGNATURES, NOISE_PARAMS, _, _noise_constants = parse_header(_read_header(NOISE_HEADER_PATH))
+NOISE_HETERO, NOISE_RICIAN = _noise_constants["NOISE_HETERO"], _noise_constants["NOISE_RICIAN"]
 
 PackJob = _structs["rdst_pack_job"]
 LrSchedule = _structs["rdst_lr_schedule"]   # passed by value to rdst_adam_step_dev
@@ -132,7 +136,8 @@ def load() -> C.CDLL:
             f"rdst_amd: {LIB_PATH} is missing. Build it with `python -m rdst_amd.build` "
             "(hipcc --offload-arch=gfx950); there is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **DATA_SIGNATURES, **LRC_SIGNATURES, **MSSSIM_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **DATA_SIGNATURES, **LRC_SIGNATURES, **MSSSIM_SIGNATURES,
+                              **NOISE_SIGNATURES}.items():
         fn = getattr(lib, name, None)
         if fn is None:  # a declared symbol the .so does not export: calling it raises
             setattr(lib, name, _missing(name))

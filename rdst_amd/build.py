@@ -38,7 +38,7 @@ def build(force: bool = False, verbose: bool = True, debug: bool = False) -> str
     srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     hdrs += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("rdst_hip.h", "rdst_hip_data.h", "rdst_hip_consistency.h",
-                                                                            "rdst_hip_msssim.h")]
+                                                                            "rdst_hip_msssim.h", "rdst_hip_noise.h")]
     jobs = []
     objs = []
     for s in srcs:

@@ -2,6 +2,8 @@
 // LR = A_y . patch . A_x^T given as a table of K taps per output (rdst_amd.data.operator_table: plain and antialiased
 // bicubic, bicubic followed by cv2's Gaussian blur, Fourier-domain truncation, ...), applied to whole images
 // (rdst_resample_sep) and inside the sampler's one launch (rdst_sample_patches_op).  sampler.hip keeps the 4-tap kernels.
+// rdst_sample_patches_noise (include/rdst_hip_noise.h) is that launch with the noise term applied in its final store: the
+// same kernel under a compile-time switch, whose off instantiation is the kernel as it was.
 //
 // Every output is formed by tapk() (tapk.h), the generalisation of sampler.hip's tap4(): acc = w[0] * v[0] rounded, then one
 // explicit fmaf per tap in ascending order; the horizontal sums of the tap rows first, then the vertical chain over them.
@@ -13,6 +15,7 @@
 // lanes along a source row; every index read from device memory is clamped before it becomes an address.
 #include "common.h"
 #include "tapk.h"
+#include "noise.h"
 #include "../../include/rdst_hip_data.h"
 
 namespace {
@@ -52,12 +55,15 @@ __global__ void __launch_bounds__(NT) vsum_kernel(const float* __restrict__ tmp,
 // is odd, so neither walk meets a bank twice), forms the horizontal sums of those rows for its BC columns into hs[hp][BC + 1]
 // and, after the last chunk, the vertical chains of its LR columns from hs.  Chunk number ch belongs to band ch % nb: that
 // band stages the whole rows, writes them to the HR output from LDS with lanes along them, and moves the label bytes.
+// NOISE: every LR value goes through noise_apply() (noise.h) on its way out, keyed by its own place in the LR array (plane =
+// b * C + c, row, column) and under the levels of patch b; nothing else changes, and `nz` is not read without it.
+template <bool NOISE>
 __global__ void __launch_bounds__(NT) sample_op_kernel(const float* __restrict__ stack, const uint8_t* __restrict__ labels,
                                                        const int* __restrict__ index, const int* __restrict__ variant,
                                                        float* __restrict__ hr, float* __restrict__ lr, uint8_t* __restrict__ lab,
                                                        int S, int C, int H, int W, int hp, int lp, int K4,
                                                        const int4* __restrict__ it, const f4* __restrict__ wt, int BC, int nb,
-                                                       int RC, int pitch) {
+                                                       int RC, int pitch, NoiseArgs nz) {
   extern __shared__ __attribute__((aligned(16))) float lds[];   // hs [hp][BC + 1], then raw [RC][pitch]
   const int hsp = BC + 1;
   float* hs = lds;
@@ -131,10 +137,16 @@ __global__ void __launch_bounds__(NT) sample_op_kernel(const float* __restrict__
     __syncthreads();   // hs of the chunk is whole; the next chunk overwrites raw
   }
   float* out = lr + ((int64_t)b * C + c) * lp * lp + c0;
+  unsigned long long seed = 0ull;
+  float p0 = 0.f, p1 = 0.f;
+  if constexpr (NOISE) seed = *nz.seed, p0 = nz.levels[2 * b], p1 = nz.levels[2 * b + 1];
   for (int e = threadIdx.x; e < lp * bcn; e += NT) {
     const int oy = e / bcn, oxl = e - oy * bcn;
     const int64_t t = (int64_t)oy * K4;
-    out[(int64_t)oy * lp + oxl] = tapk(it + t, wt + t, K4, [&](int j) { return hs[clampi(j, 0, hp - 1) * hsp + oxl]; });
+    float v = tapk(it + t, wt + t, K4, [&](int j) { return hs[clampi(j, 0, hp - 1) * hsp + oxl]; });
+    if constexpr (NOISE)
+      v = noise_apply(v, seed, (uint32_t)plane, (uint32_t)oy, (uint32_t)(c0 + oxl), nz.model, p0, p1, nz.clip_lo, nz.clip_hi);
+    out[(int64_t)oy * lp + oxl] = v;
   }
 }
 
@@ -172,10 +184,12 @@ extern "C" int rdst_resample_sep(const float* x, float* y, float* tmp, int N, in
   return rdst_launch_status(who);
 }
 
-extern "C" int rdst_sample_patches_op(const float* stack, const uint8_t* labels, const int32_t* index, const int32_t* variant,
-                                      float* hr, float* lr, uint8_t* label_out, int S, int C, int H, int W, int B, int hp, int lp,
-                                      int K, const int32_t* tap_index, const float* tap_weight, void* stream) {
-  const char* who = "rdst_sample_patches_op";
+namespace {
+
+// rdst_sample_patches_op (nz == nullptr) and rdst_sample_patches_noise: one set of refusals, one plan, one launch
+int sample_op(const char* who, const float* stack, const uint8_t* labels, const int32_t* index, const int32_t* variant, float* hr,
+              float* lr, uint8_t* label_out, int S, int C, int H, int W, int B, int hp, int lp, int K, const int32_t* tap_index,
+              const float* tap_weight, const NoiseArgs* nz, void* stream) {
   // (the checks of sampler.hip's sample_refusal, restated: that file keeps its lines)
   if (S <= 0 || C <= 0 || H <= 0 || W <= 0 || B <= 0 || hp <= 0 || lp <= 0)
     return rdst_fail(RDST_EINVAL, "%s: bad shape S=%d C=%d H=%d W=%d B=%d hp=%d lp=%d", who, S, C, H, W, B, hp, lp);
@@ -186,6 +200,8 @@ extern "C" int rdst_sample_patches_op(const float* stack, const uint8_t* labels,
   if ((int64_t)B * C * hp * hp > ((int64_t)1 << 40) || (int64_t)B * C > (1 << 20))
     return rdst_fail(RDST_EINVAL, "%s: B=%d C=%d hp=%d is too large for one launch", who, B, C, hp);
   if (int rc = table_refusal(who, "", K, tap_index, tap_weight)) return rc;
+  if (nz != nullptr)
+    if (int rc = noise_refusal(who, nz->model, nz->levels, nz->seed, nz->clip_lo, nz->clip_hi)) return rc;
   // hs [hp][BC + 1] and raw [RC][pitch]: shorter chunks first, then narrower bands
   const int pitch = hp | 1;
   int BC = min(BC_MAX, lp), RC = min(RC_MAX, hp);
@@ -198,8 +214,31 @@ extern "C" int rdst_sample_patches_op(const float* stack, const uint8_t* labels,
   const int nb = (lp + BC - 1) / BC;
   const int64_t blocks = (int64_t)B * C * nb;
   if (blocks > 0x7fffffff) return rdst_fail(RDST_EINVAL, "%s: B=%d C=%d lp=%d is too large for one launch", who, B, C, lp);
-  hipLaunchKernelGGL(sample_op_kernel, dim3((unsigned)blocks), dim3(NT), (size_t)bytes(), (hipStream_t)stream, stack, labels,
-                     index, variant, hr, lr, label_out, S, C, H, W, hp, lp, K / 4, (const int4*)tap_index,
-                     (const f4*)tap_weight, BC, nb, RC, pitch);
+  auto launch = [&](auto kern, const NoiseArgs& a) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NT), (size_t)bytes(), (hipStream_t)stream, stack, labels, index, variant,
+                       hr, lr, label_out, S, C, H, W, hp, lp, K / 4, (const int4*)tap_index, (const f4*)tap_weight, BC, nb, RC,
+                       pitch, a);
+  };
+  if (nz != nullptr) launch(sample_op_kernel<true>, *nz);
+  else launch(sample_op_kernel<false>, NoiseArgs{});
   return rdst_launch_status(who);
+}
+
+}  // namespace
+
+extern "C" int rdst_sample_patches_op(const float* stack, const uint8_t* labels, const int32_t* index, const int32_t* variant,
+                                      float* hr, float* lr, uint8_t* label_out, int S, int C, int H, int W, int B, int hp, int lp,
+                                      int K, const int32_t* tap_index, const float* tap_weight, void* stream) {
+  return sample_op("rdst_sample_patches_op", stack, labels, index, variant, hr, lr, label_out, S, C, H, W, B, hp, lp, K, tap_index,
+                   tap_weight, nullptr, stream);
+}
+
+extern "C" int rdst_sample_patches_noise(const float* stack, const uint8_t* labels, const int32_t* index, const int32_t* variant,
+                                         float* hr, float* lr, uint8_t* label_out, int S, int C, int H, int W, int B, int hp,
+                                         int lp, int K, const int32_t* tap_index, const float* tap_weight, int model,
+                                         const float* levels, const unsigned long long* seed, float clip_lo, float clip_hi,
+                                         void* stream) {
+  const NoiseArgs nz = {model, levels, seed, clip_lo, clip_hi};
+  return sample_op("rdst_sample_patches_noise", stack, labels, index, variant, hr, lr, label_out, S, C, H, W, B, hp, lp, K,
+                   tap_index, tap_weight, &nz, stream);
 }

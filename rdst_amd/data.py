@@ -31,6 +31,13 @@ bicubic of Pillow / ``interpolate(antialias=True)`` behind the SwinIR / EDSR ben
 the low-resolution acquisition of MR slices.  Each is ``LR = A_y . patch . A_x^T`` with K taps per output; the sampler, the
 whole-image resample and the test pair take any of them through one K-tap kernel family (csrc/resample.hip).
 
+Noise (``Noise``, ``add_noise``, ``noise_words``; include/rdst_hip_noise.h): the second term of ``LR = A(HR) + n``, the detector
+where the operator is the acquisition geometry: ``'gaussian'``, ``'poisson-gaussian'`` (signal-dependent, CT and photon-limited
+images) and ``'rician'`` (magnitude MRI).  The reference has no noise option; it is off by default and no gain in trained models
+is claimed.  The field is counter-based (Philox4x32-10 keyed by one 64-bit seed, one call per pixel at its own (plane, y, x)), so
+the sampler applies it in its one launch and the whole-image ``add_noise`` returns the same bits; the seed and the per-patch
+levels come from the sampler's CPU generator like everything else that is random.
+
 Out of scope, and refused where they could be asked for: augmentation other than the eight flips / transposes,
 ``return_res_image``, reading volumes from disk.
 """
@@ -498,12 +505,236 @@ def degrade(x: torch.Tensor, size, degradation: Union[str, Degradation] = "cubic
     return _Degrade.apply(x, _pair(size), d)
 
 
-def make_test_pair(hr: torch.Tensor, s: float, degradation: Union[None, str, Degradation] = None):
+# ---- the noise term: LR = A(HR) + n -----------------------------------------------------------------------------------------
+NOISE_KINDS = ("gaussian", "poisson-gaussian", "rician")
+DEFAULT_NOISE_SIGMA = 0.02      # 2 % of the unit intensity range the slices are normalised to
+DEFAULT_NOISE_GAIN = 0.01       # variance 0.01 v on top of the floor: sd 0.1 at full intensity
+# kind -> its options with their defaults, and where each goes: (model, option of p0, option of p1); None = the level 0
+_NOISE_OPTS = {"gaussian": {"sigma": DEFAULT_NOISE_SIGMA}, "poisson-gaussian": {"gain": DEFAULT_NOISE_GAIN, "sigma": DEFAULT_NOISE_SIGMA},
+               "rician": {"sigma": DEFAULT_NOISE_SIGMA}}
+_NOISE_SLOTS = {"gaussian": (_lib.NOISE_HETERO, None, "sigma"), "poisson-gaussian": (_lib.NOISE_HETERO, "gain", "sigma"),
+                "rician": (_lib.NOISE_RICIAN, "sigma", None)}
+_SEED_MASK = (1 << 64) - 1
+
+
+def _noise_level(name: str, v) -> Union[float, Tuple[float, float]]:
+    """A level as the constructor keeps it: a non-negative finite float, or a ``(lo, hi)`` pair of them with ``lo <= hi``."""
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2:
+            raise ValueError(f"Noise: {name}={v!r} must be a number or a (lo, hi) pair")
+        lo, hi = (_noise_level(name, t) for t in v)
+        if isinstance(lo, tuple) or isinstance(hi, tuple) or lo > hi:
+            raise ValueError(f"Noise: {name}={v!r} must be a (lo, hi) pair with lo <= hi")
+        return (lo, hi)
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError(f"Noise: {name}={v!r} must be a number or a (lo, hi) pair")
+    f = float(v)
+    if not math.isfinite(f) or f < 0:
+        raise ValueError(f"Noise: {name}={v!r} must be finite and not negative")
+    return f
+
+
+class Noise:
+    """The noise term of ``LR = A(HR) + n``: ``Noise(kind, **opts)``, a frozen, hashable value like ``Degradation``; a kind's
+    name is accepted wherever a ``Noise`` is and stands for its default levels.  include/rdst_hip_noise.h defines the models.
+
+    ``'gaussian'`` (``sigma``): additive, signal-independent.  ``'poisson-gaussian'`` (``gain``, ``sigma``): signal-dependent,
+    variance ``gain * max(v, 0) + sigma^2``, the Gaussian approximation of photon-limited detectors (CT).  ``'rician'``
+    (``sigma``): the modulus of the value with complex Gaussian noise, magnitude MRI.  A level is a non-negative finite float, or a
+    ``(lo, hi)`` pair with ``lo <= hi`` from which every patch (or image) draws its own level uniformly.  The defaults are
+    ``sigma = 0.02`` and ``gain = 0.01``, for intensities in [0, 1].  ``clip=None`` or ``(lo, hi)``: the noisy value is clamped
+    to that range (``(0, 1)`` keeps the inputs in the range of the clean ones)."""
+    __slots__ = ("kind", "opts", "clip")
+
+    def __init__(self, kind: str = "gaussian", clip=None, **opts):
+        if kind not in NOISE_KINDS:
+            raise ValueError(f"Noise: kind={kind!r} is not one of {NOISE_KINDS}")
+        known = _NOISE_OPTS[kind]
+        for k in opts:
+            if k not in known:
+                raise ValueError(f"Noise: {kind!r} takes no option {k!r} (it takes {tuple(known)} and clip)")
+        full = {k: _noise_level(k, v) for k, v in {**known, **opts}.items()}
+        if clip is not None:
+            if not isinstance(clip, (tuple, list)) or len(clip) != 2:
+                raise ValueError(f"Noise: clip={clip!r} must be None or a (lo, hi) pair")
+            clip = (float(clip[0]), float(clip[1]))
+            if math.isnan(clip[0]) or math.isnan(clip[1]) or clip[0] > clip[1]:
+                raise ValueError(f"Noise: clip={clip!r} must be a (lo, hi) pair with lo <= hi")
+        object.__setattr__(self, "kind", kind)
+        object.__setattr__(self, "opts", tuple(sorted(full.items())))
+        object.__setattr__(self, "clip", clip)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Noise is frozen")
+
+    __delattr__ = __setattr__
+
+    def __eq__(self, other):
+        return isinstance(other, Noise) and (self.kind, self.opts, self.clip) == (other.kind, other.opts, other.clip)
+
+    def __hash__(self):
+        return hash((self.kind, self.opts, self.clip))
+
+    def __repr__(self):
+        return "Noise(" + ", ".join([repr(self.kind)] + [f"{k}={v!r}" for k, v in self.opts] + [f"clip={self.clip!r}"]) + ")"
+
+    @classmethod
+    def of(cls, n: Union["Noise", str]) -> "Noise":
+        if isinstance(n, Noise):
+            return n
+        if isinstance(n, str):
+            return cls(n)
+        raise TypeError(f"a noise is a Noise or the name of a kind, not {type(n).__name__}")
+
+    @classmethod
+    def from_paras(cls, paras) -> Optional["Noise"]:
+        """``paras.noise_method`` (``None`` / ``''``: no noise, returned as ``None``; otherwise a kind's name) with the optional
+        ``paras.noise_sigma``, ``paras.noise_gain`` and ``paras.noise_clip``.  The reference's configuration has none of them."""
+        nm = getattr(paras, "noise_method", None)
+        if nm in (None, ""):
+            return None
+        if nm not in NOISE_KINDS:
+            raise ValueError(f"Noise.from_paras: noise_method={nm!r} is not None, '' or one of {NOISE_KINDS}")
+        opts = {k: getattr(paras, "noise_" + k) for k in _NOISE_OPTS[nm] if getattr(paras, "noise_" + k, None) is not None}
+        return cls(nm, clip=getattr(paras, "noise_clip", None), **opts)
+
+    @property
+    def model(self) -> int:
+        """RDST_NOISE_HETERO or RDST_NOISE_RICIAN."""
+        return _NOISE_SLOTS[self.kind][0]
+
+    @property
+    def ranges(self) -> Tuple[Tuple[float, float], Tuple[float, float]]:
+        """``((lo, hi) of p0, (lo, hi) of p1)``: the two levels the kernels take, a fixed level as ``(v, v)``."""
+        o = dict(self.opts)
+        out = []
+        for name in _NOISE_SLOTS[self.kind][1:]:
+            v = 0.0 if name is None else o[name]
+            out.append(v if isinstance(v, tuple) else (v, v))
+        return tuple(out)
+
+    @property
+    def clip_range(self) -> Tuple[float, float]:
+        return (-math.inf, math.inf) if self.clip is None else self.clip
+
+    def levels_from(self, u: torch.Tensor) -> torch.Tensor:
+        """Uniforms ``(n, 2)`` in [0, 1) -> the levels ``(n, 2)``: ``lo + (hi - lo) * u`` in float64, rounded once to fp32."""
+        t = _LEVEL_TERMS.get(self)
+        if t is None:       # (draw() is host time in front of every batch: the two constants are made once per value)
+            (l0, h0), (l1, h1) = self.ranges
+            t = _LEVEL_TERMS[self] = (torch.tensor([l0, l1], dtype=torch.float64), torch.tensor([h0 - l0, h1 - l1], dtype=torch.float64))
+        return (t[0] + t[1] * u.to(torch.float64)).to(torch.float32)
+
+    def draw(self, n: int, generator: Optional[torch.Generator] = None) -> Tuple[int, torch.Tensor]:
+        """One 64-bit seed, then ``torch.rand(n, 2)``: ``(seed, levels)``, the levels fp32 ``(n, 2)`` on the host."""
+        return _draw_seed(generator), self.levels_from(torch.rand(n, 2, generator=generator))
+
+
+_LEVEL_TERMS: Dict["Noise", Tuple[torch.Tensor, torch.Tensor]] = {}      # Noise -> (lo, hi - lo) of its two levels, float64
+
+
+def _draw_seed(generator: Optional[torch.Generator]) -> int:
+    return int(torch.randint(-(1 << 63), (1 << 63) - 1, (1,), dtype=torch.int64, generator=generator)) & _SEED_MASK
+
+
+def _signed64(seed: int) -> int:
+    seed = int(seed) & _SEED_MASK
+    return seed - (1 << 64) if seed >> 63 else seed
+
+
+def _host_levels(levels, n: int, what: str) -> torch.Tensor:
+    if not isinstance(levels, torch.Tensor) or levels.is_cuda or tuple(levels.shape) != (n, 2) or not levels.is_floating_point():
+        raise ValueError(f"{what}: levels must be a host tensor of shape ({n}, 2)")
+    return levels.to(torch.float32)
+
+
+def noise_words(planes: int, H: int, W: int, seed: int, device="cuda") -> torch.Tensor:
+    """The four Philox4x32-10 words of every pixel under ``seed`` (rdst_noise_words): int32 ``(planes, H, W, 4)`` bit patterns
+    on the device, key = the seed's halves, counter = ``(x, y, plane, 0)``.  What the noise of ``add_noise`` and of the sampler
+    is made from, words 0 and 1 of each pixel."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("rdst_amd.data.noise_words: the HIP path needs a GPU; there is no CPU fallback")
+    planes, H, W = int(planes), int(H), int(W)
+    if min(planes, H, W) <= 0:
+        raise ValueError(f"noise_words: sizes must be positive, got {(planes, H, W)}")
+    lib = _lib.load()
+    with torch.cuda.device(device):
+        sd = torch.tensor([_signed64(seed)], dtype=torch.int64).to(device)
+        out = torch.empty(planes, H, W, 4, dtype=torch.int32, device=device)
+        _lib.check(lib.rdst_noise_words(out.data_ptr(), planes, H, W, sd.data_ptr(), _stream()), "rdst_noise_words")
+    return out
+
+
+def add_noise(x: torch.Tensor, noise: Union[str, Noise], levels: Optional[torch.Tensor] = None, seed: Optional[int] = None,
+              generator: Optional[torch.Generator] = None, out: Optional[torch.Tensor] = None, return_draw: bool = False):
+    """The noise term on whole images (rdst_add_noise, one launch): fp32 CUDA ``(N, C, H, W)`` (or ``(C, H, W)``) -> a new tensor
+    of that shape, or ``out`` (``out=x`` works in place).  Pixel ``(n, c, y, x)`` gets the normals of ``(seed, n * C + c, y, x)``
+    under the levels of image ``n``.  ``levels``: an ``(N, 2)`` tensor of ``(p0, p1)`` per image (``Noise.ranges`` says which
+    option is which), on the host or on ``x``'s device; ``None`` draws them from ``noise``.  ``seed``: an int (its low 64 bits),
+    or ``None`` to draw one.  What is drawn comes from ``generator`` (a CPU generator; torch's default one if ``None``), the seed
+    first.  Seed and host levels go to the device in one non-blocking copy from pinned memory: the call neither waits for the
+    device nor reads from it.  ``return_draw=True`` returns ``(y, seed, levels)``, the levels as a host tensor (or the device
+    tensor that was passed).  Not differentiable."""
+    nz = Noise.of(noise)
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("add_noise: x must be a torch tensor")
+    _need_gpu("add_noise", x)
+    if x.requires_grad:
+        raise RuntimeError("add_noise is not differentiable: detach the input")
+    if x.dtype != torch.float32:
+        raise TypeError(f"add_noise: x must be float32, got {x.dtype}")
+    squeeze = x.dim() == 3
+    x4 = x.unsqueeze(0) if squeeze else x
+    if x4.dim() != 4:
+        raise ValueError("add_noise: x must have 3 or 4 dimensions")
+    N, C, H, W = x4.shape
+    if min(N, C, H, W) <= 0:
+        raise ValueError(f"add_noise: sizes must be positive, got {tuple(x4.shape)}")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.shape != x.shape or out.dtype != torch.float32
+                            or out.device != x.device or not out.is_contiguous()):
+        raise ValueError(f"add_noise: out must be a contiguous float32 {tuple(x.shape)} tensor on {x.device}")
+    if out is not None and out.data_ptr() == x.data_ptr() and not x.is_contiguous():
+        raise ValueError("add_noise: in place needs a contiguous x")
+    if seed is None:
+        seed = _draw_seed(generator)
+    seed = int(seed) & _SEED_MASK
+    dev_levels = isinstance(levels, torch.Tensor) and levels.is_cuda
+    if levels is None:
+        levels = nz.levels_from(torch.rand(N, 2, generator=generator))
+    elif dev_levels:
+        if tuple(levels.shape) != (N, 2) or levels.dtype != torch.float32 or levels.device != x.device:
+            raise ValueError(f"add_noise: device levels must be a float32 ({N}, 2) tensor on {x.device}")
+        levels = levels.contiguous()
+    else:
+        levels = _host_levels(levels, N, "add_noise")
+    x4 = x4.contiguous()
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        # the seed on its 8-byte boundary, then the host levels: one pinned buffer, one copy
+        buf = torch.empty(2 + (0 if dev_levels else 2 * N), dtype=torch.int32, pin_memory=True)
+        buf[:2].view(torch.int64)[0] = _signed64(seed)
+        if not dev_levels:
+            buf[2:].view(torch.float32).view(N, 2).copy_(levels)
+        dbuf = buf.to(x.device, non_blocking=True)
+        lv = levels.data_ptr() if dev_levels else dbuf.data_ptr() + 8
+        y = out if out is not None else torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        lo, hi = nz.clip_range
+        _lib.check(lib.rdst_add_noise(x4.data_ptr(), y.data_ptr(), N, C, H, W, nz.model, lv, dbuf.data_ptr(), lo, hi, _stream()),
+                   "rdst_add_noise")
+    return (y, seed, levels) if return_draw else y
+
+
+def make_test_pair(hr: torch.Tensor, s: float, degradation: Union[None, str, Degradation] = None,
+                   noise: Union[None, str, Noise] = None, generator: Optional[torch.Generator] = None,
+                   seed: Optional[int] = None):
     """``get_test_pair`` (datasets/basic_dataset.py:258-301) for one scale, on the device: ``hr`` fp32 CUDA ``(N, C, H, W)``
     -> ``(lr, gt, real_sr_scale)`` with ``lr = resize(hr, (H // s, W // s))``, ``gt = hr`` itself if ``(int(lr_h * s),
     int(lr_w * s)) == (H, W)`` else ``resize(hr, that size)`` (:276), and the real scale of :286.  ``degradation``: ``None``
     the plain cubic resize above; otherwise ``lr = resample(hr, (H // s, W // s), degradation)``, while ``gt``, where it needs
-    a resize, stays the plain cubic one (the reference blurs the LR image only, :276 against :112-116)."""
+    a resize, stays the plain cubic one (the reference blurs the LR image only, :276 against :112-116).  ``noise``: ``None``,
+    or a ``Noise`` (or its name) for ``lr = add_noise(lr, noise, seed=seed, generator=generator)``: one level pair per image,
+    drawn from ``generator`` (after the seed, when ``seed`` is ``None``); ``gt`` never gets any."""
     if hr.dim() != 4:
         raise ValueError("make_test_pair: hr must be (N, C, H, W)")
     H, W = hr.shape[-2:]
@@ -511,6 +742,8 @@ def make_test_pair(hr: torch.Tensor, s: float, degradation: Union[None, str, Deg
     if lr_h <= 0 or lr_w <= 0:
         raise ValueError(f"make_test_pair: a {H} x {W} slice is too small for scale {s}")
     lr = bicubic_resize(hr, (lr_h, lr_w)) if degradation is None else resample(hr, (lr_h, lr_w), degradation)
+    if noise is not None:
+        lr = add_noise(lr, noise, seed=seed, generator=generator, out=lr)
     gh, gw = int(lr_h * s), int(lr_w * s)
     gt = hr if (gh, gw) == (H, W) else bicubic_resize(hr, (gh, gw))
     return lr, gt, (gh / lr_h, gw / lr_w)
@@ -552,11 +785,13 @@ def _as_stack(images, what: str, channels: bool) -> torch.Tensor:
 
 class Draw(NamedTuple):
     """The random part of one batch: the scale, its HR patch size, the host copy of the index table and, when the batch is
-    augmented, of the variant table."""
+    augmented, of the variant table; when it is noisy, the seed of the noise field and the levels of every patch."""
     sr_factor: float
     hr_patch_size: int
     indices: torch.Tensor                       # (B, 3) int32 on the host: slice, top, left
     variants: Optional[torch.Tensor] = None     # (B,) int32 on the host: the ``tiling.dihedral`` transform of every patch
+    noise_seed: Optional[int] = None            # the 64-bit seed of the batch's noise field, in [0, 2^64)
+    noise_levels: Optional[torch.Tensor] = None     # (B, 2) fp32 on the host: (p0, p1) of every patch
 
 
 _AUGMENT = {False: 0, None: 0, True: 8, "d8": 8, "flip": 4}      # augment= -> how many of the eight transforms are drawn
@@ -593,17 +828,27 @@ class DevicePatchSampler:
     ``blur_method`` stays the reference's argument and is still refused unless ``None`` / ``''``: the Gaussian blur is asked
     for with ``degradation='cubic+gaussian'`` or ``Degradation.from_paras(paras)``.
 
+    ``noise``: ``None`` the sampler above, bit for bit, the generator consumed exactly as before; a ``Noise`` (or its name) adds
+    the noise term to ``in[b]`` in the same one launch (rdst_sample_patches_noise; ``'cubic'`` goes through it under its K = 4
+    table): ``in == add_noise(resample(out, lp, degradation), noise, levels=batch['noise_levels'], seed=batch['noise_seed'])``
+    bit for bit, while ``out`` and ``label`` are those of the clean sampler.  ``draw()`` then draws, after the variants, one 64-bit
+    seed and ``torch.rand(B, 2)``, from which every patch gets its own levels (``Noise.levels_from``); nothing else is drawn.
+    Seed and levels travel with the index table and the variants in the same pinned buffer and the same single copy (the seed
+    on an 8-byte boundary) and are returned as ``batch['noise_seed']`` / ``batch['noise_levels']`` beside ``batch['noise']``.
+    A ``draw=`` decides here too: a draw with ``noise_seed`` and ``noise_levels`` gives a noisy batch, one without a clean one.
+
     ``device='cpu'`` keeps the slices on the host: ``draw()`` works, ``sample()`` raises (there is no CPU path)."""
 
     def __init__(self, hr_images, batch_size: int, lr_patch_size: int, sr_scales: Sequence[float] = (4.0,), labels=None,
                  blur_method: Optional[str] = None, device="cuda", generator: Optional[torch.Generator] = None,
-                 augment=False, degradation: Union[None, str, Degradation] = None):
+                 augment=False, degradation: Union[None, str, Degradation] = None, noise: Union[None, str, Noise] = None):
         if blur_method not in (None, ""):
             raise ValueError(f"DevicePatchSampler: blur_method={blur_method!r} is not taken here: pass "
                              "degradation='cubic+gaussian' (cv2.GaussianBlur of the resized patch) or "
                              "degradation=Degradation.from_paras(paras); the shipped configuration has blur_method = ''")
         d = None if degradation is None else Degradation.of(degradation)
         self.degradation = None if d is None or d.kind == "cubic" else d     # None: the two 4-tap entry points, as before
+        self.noise = None if noise is None else Noise.of(noise)
         if not isinstance(augment, (bool, str, type(None))) or augment not in _AUGMENT:
             raise ValueError(f"DevicePatchSampler: augment={augment!r} is not one of False, True, 'd8', 'flip'")
         self.n_variants = _AUGMENT[augment]
@@ -653,34 +898,70 @@ class DevicePatchSampler:
         g, B = self.generator, self.batch_size
         k = int(torch.randint(len(self.sr_scales), (1,), generator=g)) if len(self.sr_scales) > 1 else 0
         hp = self.hr_patch_sizes[k]
-        if not self.n_variants:
+        noisy = self.noise is not None
+        if not self.n_variants and not noisy:
             tab = torch.empty(B, 3, dtype=torch.int32, pin_memory=self._pin)
             var = None
-        else:       # one buffer, the variants behind the index table: sample() copies it to the device as it is
-            both = torch.empty(4 * B, dtype=torch.int32, pin_memory=self._pin)
-            tab, var = both[:3 * B].view(B, 3), both[3 * B:]
+        else:       # one buffer, what else the kernel reads behind the index table: sample() copies it to the device as it is
+            vo, so, lo, total = self._layout(B, bool(self.n_variants), noisy)
+            both = torch.empty(total, dtype=torch.int32, pin_memory=self._pin)
+            tab, var = both[:3 * B].view(B, 3), both[vo:vo + B] if vo is not None else None
         tab[:, 0] = torch.randperm(self.S, generator=g)[:B]
         tab[:, 1] = torch.randint(0, self.H - hp + 1, (B,), generator=g)
         tab[:, 2] = torch.randint(0, self.W - hp + 1, (B,), generator=g)
         if var is not None:
             var[:] = torch.randint(0, self.n_variants, (B,), generator=g)
-        return Draw(self.sr_scales[k], hp, tab, var)
+        if not noisy:
+            return Draw(self.sr_scales[k], hp, tab, var)
+        seed = _draw_seed(g)
+        if so != self._layout(B, var is not None, False)[3]:
+            both[so - 1] = 0        # the pad word in front of the seed
+        both[so:so + 2].view(torch.int64)[0] = _signed64(seed)
+        lev = both[lo:].view(torch.float32).view(B, 2)
+        lev.copy_(self.noise.levels_from(torch.rand(B, 2, generator=g)))
+        return Draw(self.sr_scales[k], hp, tab, var, seed, lev)
 
-    def _packed(self, d: Draw) -> torch.Tensor:
-        """The host buffer of an augmented draw, 4 B int32: the index table, then the variants.  A draw of ``draw()`` is one
-        already; forced tables are packed into a new one."""
-        B, idx, var = self.batch_size, d.indices, d.variants
-        both = getattr(var, "_base", None)      # draw()'s two views have the whole buffer as their base
-        if (both is not None and both is idx._base and both.dtype == torch.int32 and tuple(both.shape) == (4 * B,)
+    @staticmethod
+    def _layout(B: int, variants: bool, noisy: bool):
+        """The host buffer of one draw in int32 units: ``(variants, seed, levels, total)``, ``None`` for a part it does not
+        have.  The index table (3 B), the variants (B), a pad word where the seed would not stand on an 8-byte boundary, the
+        seed (2), the levels (2 B fp32)."""
+        n = 3 * B
+        vo = n if variants else None
+        n += B if variants else 0
+        if not noisy:
+            return vo, None, None, n
+        so = n + (n & 1)
+        return vo, so, so + 2, so + 2 + 2 * B
+
+    def _packed(self, d: Draw):
+        """The host buffer of a draw with variants, noise or both, and its ``_layout``.  A draw of ``draw()`` is one already;
+        forced tables are packed into a new one."""
+        B, idx, var, lev = self.batch_size, d.indices, d.variants, d.noise_levels
+        noisy = d.noise_seed is not None
+        vo, so, lo, total = lay = self._layout(B, var is not None, noisy)
+        both = getattr(idx, "_base", None)      # draw()'s views have the whole buffer as their base
+        if (both is not None and both.dtype == torch.int32 and tuple(both.shape) == (total,)
                 and tuple(idx.shape) == (B, 3) and idx.is_contiguous() and idx.data_ptr() == both.data_ptr()
-                and tuple(var.shape) == (B,) and var.data_ptr() == both.data_ptr() + 12 * B):
-            return both
-        if not isinstance(var, torch.Tensor) or var.is_cuda or var.is_floating_point() or tuple(var.shape) != (B,):
+                and (var is None or (getattr(var, "_base", None) is both and tuple(var.shape) == (B,)
+                                     and var.data_ptr() == both.data_ptr() + 4 * vo))
+                # (a view under another dtype has a base of its own: the levels are known by the storage they share)
+                and (not noisy or (isinstance(lev, torch.Tensor) and tuple(lev.shape) == (B, 2) and lev.is_contiguous()
+                                   and lev.untyped_storage().data_ptr() == both.untyped_storage().data_ptr()
+                                   and lev.dtype == torch.float32 and lev.data_ptr() == both.data_ptr() + 4 * lo
+                                   and int(both[so:so + 2].view(torch.int64)[0]) == _signed64(d.noise_seed)))):
+            return both, lay
+        if var is not None and (not isinstance(var, torch.Tensor) or var.is_cuda or var.is_floating_point()
+                                or tuple(var.shape) != (B,)):
             raise ValueError(f"DevicePatchSampler.sample: draw.variants must be a host tensor of {B} integers")
-        both = torch.empty(4 * B, dtype=torch.int32, pin_memory=self._pin)
+        both = torch.zeros(total, dtype=torch.int32, pin_memory=self._pin)
         both[:3 * B].view(B, 3).copy_(idx)
-        both[3 * B:].copy_(var)
-        return both
+        if var is not None:
+            both[vo:vo + B].copy_(var)
+        if noisy:
+            both[so:so + 2].view(torch.int64)[0] = _signed64(d.noise_seed)
+            both[lo:].view(torch.float32).view(B, 2).copy_(_host_levels(lev, B, "DevicePatchSampler.sample: draw.noise_levels"))
+        return both, lay
 
     def batch_shapes(self, draw: Draw):
         """(shape of 'in', shape of 'out') of the batch ``draw`` leads to."""
@@ -691,6 +972,11 @@ class DevicePatchSampler:
         if self.device.type != "cuda":
             raise RuntimeError("rdst_amd.data.DevicePatchSampler.sample: the HIP path needs a GPU; there is no CPU fallback")
         d = draw if draw is not None else self.draw()
+        noisy = d.noise_seed is not None
+        if noisy != (d.noise_levels is not None):
+            raise ValueError("DevicePatchSampler.sample: draw.noise_seed and draw.noise_levels go together")
+        if noisy and self.noise is None:
+            raise ValueError("DevicePatchSampler.sample: a draw with noise needs a sampler built with noise= (it names the model)")
         lr_shape, hr_shape = self.batch_shapes(d)
         lp, hp = self.lr_patch_size, d.hr_patch_size
         lib = _lib.load()
@@ -705,18 +991,26 @@ class DevicePatchSampler:
                             or not t.is_contiguous()):
                         raise ValueError(f"DevicePatchSampler.sample: out {name} must be a contiguous float32 {shape} tensor "
                                          f"on {self.device}")
-            if d.variants is None:
+            if d.variants is None and not noisy:
                 index, variant = d.indices.to(self.device, non_blocking=True), None
-            else:
-                index = self._packed(d).to(self.device, non_blocking=True)
-                variant = index.data_ptr() + 12 * self.batch_size        # the variants sit behind the 3 B int32 of the table
+            else:       # the variants, the seed and the levels sit behind the 3 B int32 of the table, at _layout's offsets
+                both, (vo, so, lo, _) = self._packed(d)
+                index = both.to(self.device, non_blocking=True)
+                variant = index.data_ptr() + 4 * vo if vo is not None else None
             lab = None
             if self.labels is not None:
                 lab = torch.empty(hr_shape[0], 1, hp, hp, dtype=torch.uint8, device=self.device)
             stack, labels = self.hr_images.data_ptr(), self.labels.data_ptr() if lab is not None else None
             sizes = (hr.data_ptr(), lr.data_ptr(), lab.data_ptr() if lab is not None else None, self.S, self.C, self.H, self.W,
                      self.batch_size, hp, lp)
-            if self.degradation is not None:
+            if noisy:       # 'cubic' under its K = 4 table: the 4-tap kernels' bits, then the noise
+                ti, tw = _device_op_table(self.degradation or Degradation("cubic"), hp, lp, self.device)
+                clip_lo, clip_hi = self.noise.clip_range
+                _lib.check(lib.rdst_sample_patches_noise(stack, labels, index.data_ptr(), variant, *sizes, ti.shape[1],
+                                                         ti.data_ptr(), tw.data_ptr(), self.noise.model, index.data_ptr() + 4 * lo,
+                                                         index.data_ptr() + 4 * so, clip_lo, clip_hi, _stream()),
+                           "rdst_sample_patches_noise")
+            elif self.degradation is not None:
                 ti, tw = _device_op_table(self.degradation, hp, lp, self.device)
                 _lib.check(lib.rdst_sample_patches_op(stack, labels, index.data_ptr(), variant, *sizes, ti.shape[1],
                                                       ti.data_ptr(), tw.data_ptr(), _stream()), "rdst_sample_patches_op")
@@ -733,6 +1027,8 @@ class DevicePatchSampler:
             batch["variants"] = d.variants
         if self.degradation is not None:
             batch["degradation"] = self.degradation
+        if noisy:
+            batch["noise"], batch["noise_seed"], batch["noise_levels"] = self.noise, int(d.noise_seed) & _SEED_MASK, d.noise_levels
         if lab is not None:
             batch["label"] = lab.to(torch.int64)          # the dtype SegUNet_F('label-gt') takes
         return batch

@@ -305,7 +305,9 @@ class DPTrainStep:
         has finished reading them.  Labels stay in the batch for the caller's own loop: ``step()`` takes none.  An augmenting
         sampler (``augment=True``) is taken as it is: its transformed batch lands in the same tensors.  So is a sampler with a
         ``degradation`` (blurred, antialiased or Fourier-truncated inputs): the batch has the same shapes and nothing here
-        depends on how ``'in'`` was made."""
+        depends on how ``'in'`` was made.  A sampler with ``noise=`` likewise: every call draws a new seed and new levels with
+        the origins, the one launch writes the noisy ``'in'`` into the graph's tensor, and ``last_batch`` carries
+        ``'noise_seed'`` / ``'noise_levels'``, from which ``rdst_amd.data.add_noise`` reproduces that input bit for bit."""
         draw = sampler.draw()
         out = None
         if (self.graph is not None and (self.device_guard or self.loss_threshold >= GUARD_OFF)
