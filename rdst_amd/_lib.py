@@ -14,11 +14,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # RDST_HIP_LIB: load another build of the same C ABI (tools/ use it for the -DRDST_DEBUG library); the default
 # is the in-tree release library, and a missing file raises either way
 LIB_PATH = os.environ.get("RDST_HIP_LIB") or os.path.join(_HERE, "librdst_hip.so")
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rdst_hip.h")
-DATA_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rdst_hip_data.h")   # the K-tap degradations (data.py)
-LRC_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rdst_hip_consistency.h")   # LR consistency (loss/consistency.py)
-MSSSIM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rdst_hip_msssim.h")   # MS-SSIM (loss/msssim.py, metrics.py)
-NOISE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rdst_hip_noise.h")   # the noise term (data.py)
+_INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
+HEADER_PATH = os.path.join(_INCLUDE, "rdst_hip.h")
+# the side headers, prefix -> path: each gives the module <prefix>_HEADER_PATH, <prefix>_SIGNATURES and <prefix>_PARAMS
+_SIDE_HEADERS = {"DATA": os.path.join(_INCLUDE, "rdst_hip_data.h"),             # the K-tap degradations (data.py)
+                 "LRC": os.path.join(_INCLUDE, "rdst_hip_consistency.h"),       # LR consistency (loss/consistency.py)
+                 "MSSSIM": os.path.join(_INCLUDE, "rdst_hip_msssim.h"),         # MS-SSIM (loss/msssim.py, metrics.py)
+                 "NOISE": os.path.join(_INCLUDE, "rdst_hip_noise.h")}           # the noise term (data.py)
 
 _SCALARS = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
 _FIELD_SCALARS = {**_SCALARS, "int32_t": C.c_int32}
@@ -99,15 +101,14 @@ def _read_header(path=None):
 # and tools that pick arguments out of a call; the product path passes them by position)
 SIGNATURES, PARAMS, _structs, CONSTANTS = parse_header(_read_header())
 
-# the same of include/rdst_hip_data.h: entry points outside ABI_VERSION's count (a library without them gets raisers)
-DATA_SIGNATURES, DATA_PARAMS, _, _ = parse_header(_read_header(DATA_HEADER_PATH))
-# and of include/rdst_hip_consistency.h, outside the count as well
-LRC_SIGNATURES, LRC_PARAMS, _, _ = parse_header(_read_header(LRC_HEADER_PATH))
-# and of include/rdst_hip_msssim.h, outside the count as well
-MSSSIM_SIGNATURES, MSSSIM_PARAMS, _, _ = parse_header(_read_header(MSSSIM_HEADER_PATH))
-# and of include/rdst_hip_noise.h, outside the count as well; its two model numbers are its own constants
-NOISE_SIGNATURES, NOISE_PARAMS, _, _noise_constants = parse_header(_read_header(NOISE_HEADER_PATH))
-NOISE_HETERO, NOISE_RICIAN = _noise_constants["NOISE_HETERO"], _noise_constants["NOISE_RICIAN"]
+# the same of every side header: entry points outside ABI_VERSION's count (a library without them gets raisers)
+_BOUND, _side_constants = dict(SIGNATURES), {}      # every symbol load() binds; the side headers' own constants
+for _prefix, _path in _SIDE_HEADERS.items():
+    _sigs, _params, _, _consts = parse_header(_read_header(_path))
+    globals().update({_prefix + "_HEADER_PATH": _path, _prefix + "_SIGNATURES": _sigs, _prefix + "_PARAMS": _params})
+    _BOUND.update(_sigs)
+    _side_constants.update(_consts)
+NOISE_HETERO, NOISE_RICIAN = _side_constants["NOISE_HETERO"], _side_constants["NOISE_RICIAN"]   # rdst_hip_noise.h's model numbers
 
 PackJob = _structs["rdst_pack_job"]
 LrSchedule = _structs["rdst_lr_schedule"]   # passed by value to rdst_adam_step_dev
@@ -136,8 +137,7 @@ def load() -> C.CDLL:
             f"rdst_amd: {LIB_PATH} is missing. Build it with `python -m rdst_amd.build` "
             "(hipcc --offload-arch=gfx950); there is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **DATA_SIGNATURES, **LRC_SIGNATURES, **MSSSIM_SIGNATURES,
-                              **NOISE_SIGNATURES}.items():
+    for name, (res, args) in _BOUND.items():
         fn = getattr(lib, name, None)
         if fn is None:  # a declared symbol the .so does not export: calling it raises
             setattr(lib, name, _missing(name))

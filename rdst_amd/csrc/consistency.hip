@@ -26,20 +26,16 @@
 // lanes along a row or down a column of either image meet every bank once (ds_read_b32 / ds_write_b32: 32 banks per half).
 //
 // No MFMA, no atomics, no scratch; every index read from device memory is clamped before it becomes an address.
-#include "common.h"
+#include "tap_host.h"
 #include "tapk.h"
 #include "../../include/rdst_hip_consistency.h"
 
 namespace {
 
-constexpr int NT = 256;
 constexpr int NW = NT / 64;
-constexpr int LDS_BUDGET = 64 * 1024 - 256;   // the default LDS limit of a workgroup, less the static reduction slots
-constexpr int BC_MAX = 8;               // residual: LR columns per band
-constexpr int RC_MAX = 32;              // both: staged rows per chunk
-constexpr int ABR = 32, ABC = 32;       // adjoint, sparse tables: HR rows / columns per band
+constexpr int LRC_BUDGET = LDS_BUDGET - 256;   // less the static reduction slots
+constexpr int ABR = 32, ABC = 32;       // adjoint, sparse tables: HR rows / columns per band (the residual's are BC_MAX, RC_MAX)
 constexpr int ABR_DENSE = 256, ABC_DENSE = 8;
-constexpr int SG = 8;                   // staging loads a thread issues before it stores them
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
@@ -207,31 +203,12 @@ __global__ void __launch_bounds__(NT) lrc_adjoint_kernel(const float* __restrict
   }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-int table_refusal(const char* who, const char* axis, int K, const int32_t* tap_index, const float* tap_weight) {
-  if (K <= 0 || K % 4 != 0) return rdst_fail(RDST_EINVAL, "%s: K%s=%d must be a positive multiple of 4", who, axis, K);
-  if (!tap_index || !tap_weight) return rdst_fail(RDST_EINVAL, "%s: null tap table%s", who, axis);
-  if (!aligned16(tap_index) || !aligned16(tap_weight))
-    return rdst_fail(RDST_EINVAL, "%s: the tap table%s must be 16-byte aligned", who, axis);
-  return 0;
-}
-
 int shape_refusal(const char* who, int N, int C, int H, int W, int oh, int ow) {
   if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || oh <= 0 || ow <= 0)
     return rdst_fail(RDST_EINVAL, "%s: bad shape N=%d C=%d HR %d x %d LR %d x %d", who, N, C, H, W, oh, ow);
   if ((int64_t)N * C > (1 << 20) || (int64_t)N * C * H * W > ((int64_t)1 << 40) || (int64_t)N * C * oh * ow > ((int64_t)1 << 40))
     return rdst_fail(RDST_EINVAL, "%s: N=%d C=%d HR %d x %d LR %d x %d is too large for one launch", who, N, C, H, W, oh, ow);
   return 0;
-}
-
-// sums [rows][BC + 1] and raw [RC][pitch] within the LDS budget: shorter chunks first, then narrower bands
-bool fit_lds(int rows, int& BC, int& RC, int pitch, int64_t& bytes) {
-  auto need = [&]() { return ((int64_t)rows * (BC + 1) + (int64_t)RC * pitch) * (int64_t)sizeof(float); };
-  while (need() > LDS_BUDGET && RC > 1) RC >>= 1;
-  while (need() > LDS_BUDGET && BC > 1) BC >>= 1;
-  bytes = need();
-  return bytes <= LDS_BUDGET;
 }
 
 }  // namespace
@@ -259,7 +236,7 @@ extern "C" int rdst_lrc_residual(const float* pred, const float* lr, int N, int 
   const int pitch = W | 1;
   int BC = min(BC_MAX, ow), RC = min(RC_MAX, H);
   int64_t bytes;
-  if (!fit_lds(H, BC, RC, pitch, bytes))
+  if (!fit_lds(H, BC, RC, pitch, LRC_BUDGET, bytes))
     return rdst_fail(RDST_ENOTSUP, "%s: H=%d W=%d is larger than the LDS holds (one column of sums and one row need %lld bytes)",
                      who, H, W, (long long)bytes);
   const int nb = (ow + BC - 1) / BC;
@@ -297,7 +274,7 @@ extern "C" int rdst_lrc_adjoint(const float* g, int N, int C, int oh, int ow, in
   const int pitch = ow | 1;
   int BC = min(dense ? ABC_DENSE : ABC, W), RC = min(RC_MAX, oh);
   int64_t bytes;
-  if (!fit_lds(oh, BC, RC, pitch, bytes))
+  if (!fit_lds(oh, BC, RC, pitch, LRC_BUDGET, bytes))
     return rdst_fail(RDST_ENOTSUP, "%s: LR %d x %d is larger than the LDS holds (one column of sums and one row need %lld bytes)",
                      who, oh, ow, (long long)bytes);
   const int nbr = (H + BR - 1) / BR, nbc = (W + BC - 1) / BC;

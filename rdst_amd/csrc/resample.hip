@@ -1,7 +1,8 @@
 // K-tap degradations of the device data path (rdst_amd/data.py, include/rdst_hip_data.h): any separable linear operator
 // LR = A_y . patch . A_x^T given as a table of K taps per output (rdst_amd.data.operator_table: plain and antialiased
 // bicubic, bicubic followed by cv2's Gaussian blur, Fourier-domain truncation, ...), applied to whole images
-// (rdst_resample_sep) and inside the sampler's one launch (rdst_sample_patches_op).  sampler.hip keeps the 4-tap kernels.
+// (rdst_resample_sep) and inside the sampler's one launch (rdst_sample_patches_op).  sampler.hip has the 4-tap kernels; the
+// argument checks and the LDS fit both files make are tap_host.h's.
 // rdst_sample_patches_noise (include/rdst_hip_noise.h) is that launch with the noise term applied in its final store: the
 // same kernel under a compile-time switch, whose off instantiation is the kernel as it was.
 //
@@ -13,18 +14,12 @@
 //
 // No MFMA, no atomics, no scratch.  Tables are read as int4 / float4 (K % 4 == 0, 16-byte aligned), pixels as dwords with
 // lanes along a source row; every index read from device memory is clamped before it becomes an address.
-#include "common.h"
+#include "tap_host.h"
 #include "tapk.h"
 #include "noise.h"
 #include "../../include/rdst_hip_data.h"
 
 namespace {
-
-constexpr int NT = 256;
-constexpr int LDS_BUDGET = 64 * 1024;   // the sampler's budget (the default dynamic-LDS limit)
-constexpr int BC_MAX = 8;               // LR columns per band
-constexpr int RC_MAX = 32;              // rows of the turned patch per staged chunk
-constexpr int SG = 8;                   // staging loads a thread issues before it stores them
 
 // ---- rdst_resample_sep: the horizontal sums of every source row, then the vertical chains; one thread per value -------
 __global__ void __launch_bounds__(NT) hsum_kernel(const float* __restrict__ x, float* __restrict__ tmp, int W, int ow, int Kx4,
@@ -150,16 +145,6 @@ __global__ void __launch_bounds__(NT) sample_op_kernel(const float* __restrict__
   }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-int table_refusal(const char* who, const char* axis, int K, const int32_t* tap_index, const float* tap_weight) {
-  if (K <= 0 || K % 4 != 0) return rdst_fail(RDST_EINVAL, "%s: K%s=%d must be a positive multiple of 4", who, axis, K);
-  if (!tap_index || !tap_weight) return rdst_fail(RDST_EINVAL, "%s: null tap table%s", who, axis);
-  if (!aligned16(tap_index) || !aligned16(tap_weight))
-    return rdst_fail(RDST_EINVAL, "%s: the tap table%s must be 16-byte aligned", who, axis);
-  return 0;
-}
-
 }  // namespace
 
 extern "C" int rdst_resample_sep(const float* x, float* y, float* tmp, int N, int C, int H, int W, int oh, int ow, int Ky,
@@ -190,32 +175,21 @@ namespace {
 int sample_op(const char* who, const float* stack, const uint8_t* labels, const int32_t* index, const int32_t* variant, float* hr,
               float* lr, uint8_t* label_out, int S, int C, int H, int W, int B, int hp, int lp, int K, const int32_t* tap_index,
               const float* tap_weight, const NoiseArgs* nz, void* stream) {
-  // (the checks of sampler.hip's sample_refusal, restated: that file keeps its lines)
-  if (S <= 0 || C <= 0 || H <= 0 || W <= 0 || B <= 0 || hp <= 0 || lp <= 0)
-    return rdst_fail(RDST_EINVAL, "%s: bad shape S=%d C=%d H=%d W=%d B=%d hp=%d lp=%d", who, S, C, H, W, B, hp, lp);
-  if (hp > H || hp > W) return rdst_fail(RDST_EINVAL, "%s: a %d x %d patch does not fit a %d x %d slice", who, hp, hp, H, W);
-  if (!stack || !index || !hr || !lr) return rdst_fail(RDST_EINVAL, "%s: null pointer", who);
-  if ((labels != nullptr) != (label_out != nullptr))
-    return rdst_fail(RDST_EINVAL, "%s: labels and label_out go together", who);
-  if ((int64_t)B * C * hp * hp > ((int64_t)1 << 40) || (int64_t)B * C > (1 << 20))
-    return rdst_fail(RDST_EINVAL, "%s: B=%d C=%d hp=%d is too large for one launch", who, B, C, hp);
+  if (int rc = sample_refusal(who, stack, labels, index, hr, lr, label_out, S, C, H, W, B, hp, lp)) return rc;
   if (int rc = table_refusal(who, "", K, tap_index, tap_weight)) return rc;
   if (nz != nullptr)
     if (int rc = noise_refusal(who, nz->model, nz->levels, nz->seed, nz->clip_lo, nz->clip_hi)) return rc;
-  // hs [hp][BC + 1] and raw [RC][pitch]: shorter chunks first, then narrower bands
-  const int pitch = hp | 1;
+  const int pitch = hp | 1;   // hs [hp][BC + 1] and raw [RC][pitch]
   int BC = min(BC_MAX, lp), RC = min(RC_MAX, hp);
-  auto bytes = [&]() { return ((int64_t)hp * (BC + 1) + (int64_t)RC * pitch) * (int64_t)sizeof(float); };
-  while (bytes() > LDS_BUDGET && RC > 1) RC >>= 1;
-  while (bytes() > LDS_BUDGET && BC > 1) BC >>= 1;
-  if (bytes() > LDS_BUDGET)
+  int64_t bytes;
+  if (!fit_lds(hp, BC, RC, pitch, LDS_BUDGET, bytes))
     return rdst_fail(RDST_ENOTSUP, "%s: hp=%d is wider than the LDS holds (one column of sums and one row need %lld bytes)", who,
-                     hp, (long long)bytes());
+                     hp, (long long)bytes);
   const int nb = (lp + BC - 1) / BC;
   const int64_t blocks = (int64_t)B * C * nb;
   if (blocks > 0x7fffffff) return rdst_fail(RDST_EINVAL, "%s: B=%d C=%d lp=%d is too large for one launch", who, B, C, lp);
   auto launch = [&](auto kern, const NoiseArgs& a) {
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NT), (size_t)bytes(), (hipStream_t)stream, stack, labels, index, variant,
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NT), (size_t)bytes, (hipStream_t)stream, stack, labels, index, variant,
                        hr, lr, label_out, S, C, H, W, hp, lp, K / 4, (const int4*)tap_index, (const f4*)tap_weight, BC, nb, RC,
                        pitch, a);
   };

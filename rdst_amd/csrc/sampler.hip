@@ -22,14 +22,15 @@
 // same tap4() chains over the turned rows and columns (the chain is not flip invariant in fp32, so resizing first and turning
 // afterwards would give other bits).  Reads run with lanes along a source row and stores with lanes along an output row: a
 // flipped row is a reversed run, and the four transposed variants pass through 32 x 32 LDS blocks with rows of 33 floats.
-#include "common.h"
+//
+// Both sampler entry points share one host plan (sample_tap4).  At hp = 4 lp they have a kernel each, two designs (a thread
+// per 4 x 4 group; a workgroup per 32 x 32 block through LDS); at any other ratio one kernel source, sample_tab_kernel<V4, D8>,
+// whose D8 == false instantiation has no turn in it.  The argument checks are tap_host.h's, f4 and clampi tapk.h's.
+#include "tap_host.h"
+#include "tapk.h"
 
 namespace {
 
-constexpr int NT = 256;
-constexpr int LDS_BUDGET = 64 * 1024;   // the table path's tile of HR rows (the default dynamic-LDS limit)
-
-typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));   // four floats at dword alignment
 struct __attribute__((packed, aligned(1))) u8x4 { uint32_t v; };     // four label bytes at any address
 
@@ -37,8 +38,6 @@ struct __attribute__((packed, aligned(1))) u8x4 { uint32_t v; };     // four lab
 __device__ __forceinline__ float tap4(float v0, float v1, float v2, float v3, float w0, float w1, float w2, float w3) {
   return fmaf(w3, v3, fmaf(w2, v2, fmaf(w1, v1, __fmul_rn(w0, v0))));
 }
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // ---- rdst_resize_bicubic: one thread per output pixel ----------------------------------------------------------------
 __global__ void __launch_bounds__(NT) resize_kernel(const float* __restrict__ x, float* __restrict__ y, int H, int W, int oh,
@@ -116,7 +115,7 @@ __global__ void __launch_bounds__(NT) sample4_kernel(const float* __restrict__ s
 }
 
 // band `band` of nb: its LR rows [o0, o1), the HR rows it stages [tap_lo, tap_hi), owns [own_lo, own_hi) and walks [row_lo,
-// row_hi).  (sample_tab_kernel's own arithmetic; it keeps its lines, and with them its instructions, as they were)
+// row_hi)
 struct Band {
   int o0, o1, tap_lo, tap_hi, own_lo, own_hi, row_lo, row_hi;
 };
@@ -150,56 +149,6 @@ __device__ __forceinline__ void lr_rows_from_tile(const float* tile, float* out,
     const float h3 = tap4(r3[x0], r3[x1], r3[x2], r3[x3], fx.x, fx.y, fx.z, fx.w);
     out[(int64_t)oy * lp + ox] = tap4(h0, h1, h2, h3, fy.x, fy.y, fy.z, fy.w);
   }
-}
-
-// ---- rdst_sample_patches, any ratio: one workgroup per (patch, channel, band of LB rows of the LR patch) --------------
-// The bands partition the rows of the HR patch: band k owns the rows from the first tap row of its first LR row up to the
-// first tap row of the next band (band 0 from row 0, the last band to row hp - 1).  A workgroup walks the rows it owns and
-// the tap rows of its LR rows once: an owned row goes to the HR output, a tap row into the LDS tile, most rows both, from one
-// load.  The tap rows a band shares with the next one (three at most when shrinking) are read by both, from the L2.  Then
-// the LR rows are formed from the tile.  V4: hp % 4 == 0 and 16-byte aligned outputs, four pixels per lane and access.
-template <bool V4>
-__global__ void __launch_bounds__(NT) sample_tab_kernel(const float* __restrict__ stack, const uint8_t* __restrict__ labels,
-                                                        const int* __restrict__ index, float* __restrict__ hr,
-                                                        float* __restrict__ lr, uint8_t* __restrict__ lab, int S, int C,
-                                                        int H, int W, int hp, int lp, const int4* __restrict__ it,
-                                                        const f4* __restrict__ wt, int LB, int nb, int max_rows) {
-  extern __shared__ __attribute__((aligned(16))) float tile[];   // [max_rows][hp]
-  const int band = (int)(blockIdx.x % (unsigned)nb);
-  const int plane = (int)(blockIdx.x / (unsigned)nb);
-  const int c = plane % C, b = plane / C;
-  const int o0 = band * LB, o1 = min(o0 + LB, lp);
-  const Window w = window_of(index, b, S, H, W, hp);
-  const int tap_lo = clampi(it[o0].x, 0, hp - 1);
-  const int tap_hi = min(max(clampi(it[o1 - 1].w, 0, hp - 1) + 1, tap_lo + 1), tap_lo + max_rows);   // staged: [tap_lo, tap_hi)
-  const int own_lo = band == 0 ? 0 : tap_lo;
-  const int own_hi = band == nb - 1 ? hp : max(clampi(it[o1].x, 0, hp - 1), own_lo);
-  const int row_lo = min(own_lo, tap_lo), row_hi = max(own_hi, tap_hi);
-  const float* src = stack + ((w.slice * C + c) * H + w.top) * W + w.left;
-  float* dst = hr + ((int64_t)b * C + c) * hp * hp;
-  const uint8_t* ls = labels != nullptr && c == 0 ? labels + (w.slice * H + w.top) * W + w.left : nullptr;
-  uint8_t* ld = lab + (int64_t)b * hp * hp;
-  constexpr int V = V4 ? 4 : 1;
-  const int per_row = hp / V;
-  for (int e = threadIdx.x; e < (row_hi - row_lo) * per_row; e += NT) {
-    const int r = row_lo + e / per_row, col = (e % per_row) * V;
-    const bool own = r >= own_lo && r < own_hi, tap = r >= tap_lo && r < tap_hi;
-    if (!own && !tap) continue;
-    if (V4) {
-      const f4 v = *reinterpret_cast<const f4u*>(src + (int64_t)r * W + col);
-      if (own) *reinterpret_cast<f4*>(dst + (int64_t)r * hp + col) = v;
-      if (tap) *reinterpret_cast<f4*>(tile + (r - tap_lo) * hp + col) = v;
-      if (own && ls != nullptr)
-        *reinterpret_cast<uint32_t*>(ld + (int64_t)r * hp + col) = reinterpret_cast<const u8x4*>(ls + (int64_t)r * W + col)->v;
-    } else {
-      const float v = src[(int64_t)r * W + col];
-      if (own) dst[(int64_t)r * hp + col] = v;
-      if (tap) tile[(r - tap_lo) * hp + col] = v;
-      if (own && ls != nullptr) ld[(int64_t)r * hp + col] = ls[(int64_t)r * W + col];
-    }
-  }
-  __syncthreads();
-  lr_rows_from_tile(tile, lr + ((int64_t)b * C + c) * lp * lp, hp, lp, o0, o1, tap_lo, tap_hi - tap_lo, it, wt);
 }
 
 // ---- rdst_sample_patches_d8 --------------------------------------------------------------------------------------------------
@@ -288,25 +237,34 @@ __global__ void __launch_bounds__(NT) sample4_d8_kernel(const float* __restrict_
   }
 }
 
-// Any ratio: sample_tab_kernel's bands over the rows of the TURNED patch.  A flip-only variant walks its rows as the plain
-// kernel does, each from the source row and the run of columns it mirrors.  A transposed variant covers the rows it walks with
-// TB x TB blocks: a block of source rows is read with lanes along them into LDS (behind the tile: all LDS is dynamic, so the
-// tile keeps its 16-byte base) and written out with lanes along the output rows, to the HR output, the tile, or both.
-template <bool V4>
-__global__ void __launch_bounds__(NT) sample_tab_d8_kernel(const float* __restrict__ stack, const uint8_t* __restrict__ labels,
-                                                           const int* __restrict__ index, const int* __restrict__ variant,
-                                                           float* __restrict__ hr, float* __restrict__ lr,
-                                                           uint8_t* __restrict__ lab, int S, int C, int H, int W, int hp, int lp,
-                                                           const int4* __restrict__ it, const f4* __restrict__ wt, int LB, int nb,
-                                                           int max_rows) {
-  extern __shared__ __attribute__((aligned(16))) float tile[];   // [max_rows][hp], then blk [TB][TBP], then lblk [TB][TBL]
+// ---- rdst_sample_patches and rdst_sample_patches_d8, any ratio: one workgroup per (patch, channel, band of LB rows of the LR
+// patch) ------------------------------------------------------------------------------------------------------------------
+// The bands partition the rows of the HR patch: band k owns the rows from the first tap row of its first LR row up to the
+// first tap row of the next band (band 0 from row 0, the last band to row hp - 1).  A workgroup walks the rows it owns and
+// the tap rows of its LR rows once: an owned row goes to the HR output, a tap row into the LDS tile, most rows both, from one
+// load.  The tap rows a band shares with the next one (three at most when shrinking) are read by both, from the L2.  Then
+// the LR rows are formed from the tile.  V4: hp % 4 == 0 and 16-byte aligned outputs, four pixels per lane and access.
+// D8: the rows are those of the TURNED patch.  A flip-only variant walks them as the plain kernel does, each from the source
+// row and the run of columns it mirrors.  A transposed variant covers the rows it walks with TB x TB blocks: a block of source
+// rows is read with lanes along them into LDS (behind the tile: all LDS is dynamic, so the tile keeps its 16-byte base) and
+// written out with lanes along the output rows, to the HR output, the tile, or both.  Without D8 `variant` is not read, and
+// the turn, the mirrored addresses and the transposed branch are not compiled.
+template <bool V4, bool D8>
+__global__ void __launch_bounds__(NT) sample_tab_kernel(const float* __restrict__ stack, const uint8_t* __restrict__ labels,
+                                                        const int* __restrict__ index, const int* __restrict__ variant,
+                                                        float* __restrict__ hr, float* __restrict__ lr,
+                                                        uint8_t* __restrict__ lab, int S, int C, int H, int W, int hp, int lp,
+                                                        const int4* __restrict__ it, const f4* __restrict__ wt, int LB, int nb,
+                                                        int max_rows) {
+  extern __shared__ __attribute__((aligned(16))) float tile[];   // [max_rows][hp]; D8: then blk [TB][TBP], then lblk [TB][TBL]
   float(*blk)[TBP] = reinterpret_cast<float(*)[TBP]>(tile + max_rows * hp);
   uint8_t(*lblk)[TBL] = reinterpret_cast<uint8_t(*)[TBL]>(blk + TB);
   const int band = (int)(blockIdx.x % (unsigned)nb);
   const int plane = (int)(blockIdx.x / (unsigned)nb);
   const int c = plane % C, b = plane / C;
   const Window w = window_of(index, b, S, H, W, hp);
-  const Turn u = turn_of(variant, b);
+  Turn u = {false, false, false};   // (constants without D8: the mirrored addresses below fold to the plain ones)
+  if constexpr (D8) u = turn_of(variant, b);
   const Band bd = band_of(it, band, nb, LB, hp, lp, max_rows);
   const float* src = stack + ((w.slice * C + c) * H + w.top) * W + w.left;
   float* dst = hr + ((int64_t)b * C + c) * hp * hp;
@@ -336,7 +294,7 @@ __global__ void __launch_bounds__(NT) sample_tab_d8_kernel(const float* __restri
         if (own && ls != nullptr) ld[(int64_t)r * hp + col] = ls[at];
       }
     }
-  } else {
+  } else if constexpr (D8) {
     constexpr int TPR = TB / V;   // threads along an output row
     const int cc = threadIdx.x % TB, q0 = (int)(threadIdx.x % TPR) * V;
     for (int i0 = bd.row_lo; i0 < bd.row_hi; i0 += TB) {
@@ -388,8 +346,6 @@ __global__ void __launch_bounds__(NT) sample_tab_d8_kernel(const float* __restri
   lr_rows_from_tile(tile, lr + ((int64_t)b * C + c) * lp * lp, hp, lp, bd.o0, bd.o1, bd.tap_lo, bd.tap_hi - bd.tap_lo, it, wt);
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int rdst_resize_bicubic(const float* x, float* y, int N, int C, int H, int W, int oh, int ow,
@@ -400,7 +356,7 @@ extern "C" int rdst_resize_bicubic(const float* x, float* y, int N, int C, int H
     return rdst_fail(RDST_EINVAL, "%s: bad shape N=%d C=%d H=%d W=%d -> %d x %d", who, N, C, H, W, oh, ow);
   if (!x || !y || !tap_index_y || !tap_weight_y || !tap_index_x || !tap_weight_x)
     return rdst_fail(RDST_EINVAL, "%s: null pointer", who);
-  if (!aligned16(tap_index_y) || !aligned16(tap_weight_y) || !aligned16(tap_index_x) || !aligned16(tap_weight_x))
+  if (!rdst_aligned(16, {tap_index_y, tap_weight_y, tap_index_x, tap_weight_x}, {}))
     return rdst_fail(RDST_EINVAL, "%s: the tap tables must be 16-byte aligned", who);
   const int64_t total = (int64_t)N * C * oh * ow;
   const int64_t blocks = (total + NT - 1) / NT;
@@ -413,26 +369,6 @@ extern "C" int rdst_resize_bicubic(const float* x, float* y, int N, int C, int H
 
 namespace {
 
-// the argument checks of both sampler entry points, before anything is launched
-int sample_refusal(const char* who, const float* stack, const uint8_t* labels, const int32_t* index, const float* hr,
-                   const float* lr, const uint8_t* label_out, int S, int C, int H, int W, int B, int hp, int lp) {
-  if (S <= 0 || C <= 0 || H <= 0 || W <= 0 || B <= 0 || hp <= 0 || lp <= 0)
-    return rdst_fail(RDST_EINVAL, "%s: bad shape S=%d C=%d H=%d W=%d B=%d hp=%d lp=%d", who, S, C, H, W, B, hp, lp);
-  if (hp > H || hp > W) return rdst_fail(RDST_EINVAL, "%s: a %d x %d patch does not fit a %d x %d slice", who, hp, hp, H, W);
-  if (!stack || !index || !hr || !lr) return rdst_fail(RDST_EINVAL, "%s: null pointer", who);
-  if ((labels != nullptr) != (label_out != nullptr))
-    return rdst_fail(RDST_EINVAL, "%s: labels and label_out go together", who);
-  if ((int64_t)B * C * hp * hp > ((int64_t)1 << 40) || (int64_t)B * C > (1 << 20))
-    return rdst_fail(RDST_EINVAL, "%s: B=%d C=%d hp=%d is too large for one launch", who, B, C, hp);
-  return 0;
-}
-
-int table_refusal(const char* who, const int32_t* tap_index, const float* tap_weight, int hp, int lp) {
-  if (!tap_index || !tap_weight) return rdst_fail(RDST_EINVAL, "%s: hp=%d lp=%d needs the tap table", who, hp, lp);
-  if (!aligned16(tap_index) || !aligned16(tap_weight)) return rdst_fail(RDST_EINVAL, "%s: the tap table must be 16-byte aligned", who);
-  return 0;
-}
-
 // LB LR rows per band: the largest power of two whose tap rows, (LB - 1) hp / lp + 5 at most, fit a tile of `budget` bytes
 // (0 if not even one row's do)
 int band_rows(int hp, int lp, int budget, int* max_rows) {
@@ -444,6 +380,45 @@ int band_rows(int hp, int lp, int budget, int* max_rows) {
   return 0;
 }
 
+// rdst_sample_patches (variant == nullptr) and rdst_sample_patches_d8 behind their argument checks: one plan, one launch
+int sample_tap4(const char* who, const float* stack, const uint8_t* labels, const int32_t* index, const int32_t* variant, float* hr,
+                float* lr, uint8_t* label_out, int S, int C, int H, int W, int B, int hp, int lp, const int32_t* tap_index,
+                const float* tap_weight, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const bool d8 = variant != nullptr;
+  const bool wide = hp % 4 == 0 && rdst_aligned(16, {hr}, {}) && rdst_aligned(4, {label_out}, {});
+  if (hp == 4 * lp && wide) {
+    if (d8) {
+      const int nbk = (hp + TB - 1) / TB;
+      const int64_t blocks = (int64_t)B * C * nbk * nbk;
+      if (blocks > 0x7fffffff) return rdst_fail(RDST_EINVAL, "%s: B=%d C=%d hp=%d is too large for one launch", who, B, C, hp);
+      hipLaunchKernelGGL(sample4_d8_kernel, dim3((unsigned)blocks), dim3(NT), 0, st, stack, labels, index, variant, hr, lr,
+                         label_out, S, C, H, W, lp, nbk);
+    } else {
+      const int64_t total = (int64_t)B * C * lp * lp;
+      hipLaunchKernelGGL(sample4_kernel, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, st, stack, labels, index, hr, lr,
+                         label_out, S, C, H, W, lp, total);
+    }
+    return rdst_launch_status(who);
+  }
+  if (!tap_index || !tap_weight) return rdst_fail(RDST_EINVAL, "%s: hp=%d lp=%d needs the tap table", who, hp, lp);
+  if (!rdst_aligned(16, {tap_index, tap_weight}, {})) return rdst_fail(RDST_EINVAL, "%s: the tap table must be 16-byte aligned", who);
+  const int blk_bytes = d8 ? BLK_BYTES : 0;   // the transposing block shares the dynamic LDS
+  int max_rows = 0;
+  const int LB = band_rows(hp, lp, LDS_BUDGET - blk_bytes, &max_rows);
+  if (LB < 1) return rdst_fail(RDST_ENOTSUP, "%s: hp=%d is wider than the table path's tile holds", who, hp);
+  const int nb = (lp + LB - 1) / LB;
+  const int smem = max_rows * hp * (int)sizeof(float) + blk_bytes;
+  const unsigned grid = (unsigned)((int64_t)B * C * nb);
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), smem, st, stack, labels, index, variant, hr, lr, label_out, S, C, H, W, hp, lp,
+                       (const int4*)tap_index, (const f4*)tap_weight, LB, nb, max_rows);
+  };
+  if (!d8) wide ? launch(sample_tab_kernel<true, false>) : launch(sample_tab_kernel<false, false>);
+  else wide ? launch(sample_tab_kernel<true, true>) : launch(sample_tab_kernel<false, true>);
+  return rdst_launch_status(who);
+}
+
 }  // namespace
 
 extern "C" int rdst_sample_patches(const float* stack, const uint8_t* labels, const int32_t* index, float* hr, float* lr,
@@ -451,28 +426,7 @@ extern "C" int rdst_sample_patches(const float* stack, const uint8_t* labels, co
                                    const int32_t* tap_index, const float* tap_weight, void* stream) {
   const char* who = "rdst_sample_patches";
   if (int rc = sample_refusal(who, stack, labels, index, hr, lr, label_out, S, C, H, W, B, hp, lp)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const bool wide = hp % 4 == 0 && aligned16(hr) && (label_out == nullptr || ((uintptr_t)label_out & 3) == 0);
-  if (hp == 4 * lp && wide) {
-    const int64_t total = (int64_t)B * C * lp * lp;
-    hipLaunchKernelGGL(sample4_kernel, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, st, stack, labels, index, hr, lr,
-                       label_out, S, C, H, W, lp, total);
-    return rdst_launch_status(who);
-  }
-  if (int rc = table_refusal(who, tap_index, tap_weight, hp, lp)) return rc;
-  int max_rows = 0;
-  const int LB = band_rows(hp, lp, LDS_BUDGET, &max_rows);
-  if (LB < 1) return rdst_fail(RDST_ENOTSUP, "%s: hp=%d is wider than the table path's tile holds", who, hp);
-  const int nb = (lp + LB - 1) / LB;
-  const int smem = max_rows * hp * (int)sizeof(float);
-  const unsigned grid = (unsigned)((int64_t)B * C * nb);
-  if (wide)
-    hipLaunchKernelGGL(sample_tab_kernel<true>, dim3(grid), dim3(NT), smem, st, stack, labels, index, hr, lr, label_out, S, C, H,
-                       W, hp, lp, (const int4*)tap_index, (const f4*)tap_weight, LB, nb, max_rows);
-  else
-    hipLaunchKernelGGL(sample_tab_kernel<false>, dim3(grid), dim3(NT), smem, st, stack, labels, index, hr, lr, label_out, S, C,
-                       H, W, hp, lp, (const int4*)tap_index, (const f4*)tap_weight, LB, nb, max_rows);
-  return rdst_launch_status(who);
+  return sample_tap4(who, stack, labels, index, nullptr, hr, lr, label_out, S, C, H, W, B, hp, lp, tap_index, tap_weight, stream);
 }
 
 extern "C" int rdst_sample_patches_d8(const float* stack, const uint8_t* labels, const int32_t* index, const int32_t* variant,
@@ -481,28 +435,5 @@ extern "C" int rdst_sample_patches_d8(const float* stack, const uint8_t* labels,
   const char* who = "rdst_sample_patches_d8";
   if (int rc = sample_refusal(who, stack, labels, index, hr, lr, label_out, S, C, H, W, B, hp, lp)) return rc;
   if (!variant) return rdst_fail(RDST_EINVAL, "%s: null pointer", who);
-  hipStream_t st = (hipStream_t)stream;
-  const bool wide = hp % 4 == 0 && aligned16(hr) && (label_out == nullptr || ((uintptr_t)label_out & 3) == 0);
-  if (hp == 4 * lp && wide) {
-    const int nbk = (hp + TB - 1) / TB;
-    const int64_t blocks = (int64_t)B * C * nbk * nbk;
-    if (blocks > 0x7fffffff) return rdst_fail(RDST_EINVAL, "%s: B=%d C=%d hp=%d is too large for one launch", who, B, C, hp);
-    hipLaunchKernelGGL(sample4_d8_kernel, dim3((unsigned)blocks), dim3(NT), 0, st, stack, labels, index, variant, hr, lr,
-                       label_out, S, C, H, W, lp, nbk);
-    return rdst_launch_status(who);
-  }
-  if (int rc = table_refusal(who, tap_index, tap_weight, hp, lp)) return rc;
-  int max_rows = 0;
-  const int LB = band_rows(hp, lp, LDS_BUDGET - BLK_BYTES, &max_rows);   // the transposing block shares the dynamic LDS
-  if (LB < 1) return rdst_fail(RDST_ENOTSUP, "%s: hp=%d is wider than the table path's tile holds", who, hp);
-  const int nb = (lp + LB - 1) / LB;
-  const int smem = max_rows * hp * (int)sizeof(float) + BLK_BYTES;
-  const unsigned grid = (unsigned)((int64_t)B * C * nb);
-  if (wide)
-    hipLaunchKernelGGL(sample_tab_d8_kernel<true>, dim3(grid), dim3(NT), smem, st, stack, labels, index, variant, hr, lr,
-                       label_out, S, C, H, W, hp, lp, (const int4*)tap_index, (const f4*)tap_weight, LB, nb, max_rows);
-  else
-    hipLaunchKernelGGL(sample_tab_d8_kernel<false>, dim3(grid), dim3(NT), smem, st, stack, labels, index, variant, hr, lr,
-                       label_out, S, C, H, W, hp, lp, (const int4*)tap_index, (const f4*)tap_weight, LB, nb, max_rows);
-  return rdst_launch_status(who);
+  return sample_tap4(who, stack, labels, index, variant, hr, lr, label_out, S, C, H, W, B, hp, lp, tap_index, tap_weight, stream);
 }

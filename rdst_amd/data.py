@@ -38,11 +38,17 @@ is claimed.  The field is counter-based (Philox4x32-10 keyed by one 64-bit seed,
 the sampler applies it in its one launch and the whole-image ``add_noise`` returns the same bits; the seed and the per-patch
 levels come from the sampler's CPU generator like everything else that is random.
 
+One of each on the host side: the whole-image calls check their input through ``_whole_images``; every device table is
+``_on_device`` of its host table (``tap_table``, ``operator_table``, ``adjoint_table``), cached per arguments and device;
+``Degradation`` and ``Noise`` are ``_Frozen`` values; and every draw, plain or not, is the one pinned buffer ``_layout``
+describes, which ``sample()`` copies to the device once and from which the four C entry points are chosen as before.
+
 Out of scope, and refused where they could be asked for: augmentation other than the eight flips / transposes,
 ``return_res_image``, reading volumes from disk.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Dict, NamedTuple, Optional, Sequence, Tuple, Union
 
@@ -79,15 +85,20 @@ def tap_table(n_in: int, n_out: int) -> Tuple[np.ndarray, np.ndarray]:
 _TABLES: Dict[tuple, Tuple[torch.Tensor, torch.Tensor]] = {}
 
 
-def _device_table(n_in: int, n_out: int, device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
-    """``tap_table`` on the device, the weights rounded once to fp32; cached per (in, out, device)."""
-    key = (int(n_in), int(n_out), device.type, device.index)
+def _on_device(table, device: torch.device, *args) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``table(*args)`` on the device, the weights rounded once to fp32; cached per (table, arguments, device)."""
+    key = (table, *args, device.type, device.index)
     tab = _TABLES.get(key)
     if tab is None:
-        index, weight = tap_table(n_in, n_out)
-        tab = (torch.from_numpy(index).to(device), torch.from_numpy(weight.astype(np.float32)).to(device))
-        _TABLES[key] = tab
+        index, weight = table(*args)
+        tab = _TABLES[key] = (torch.from_numpy(np.ascontiguousarray(index)).to(device),
+                              torch.from_numpy(weight.astype(np.float32)).to(device))
     return tab
+
+
+def _device_table(n_in: int, n_out: int, device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``tap_table`` on the device; cached per (in, out, device)."""
+    return _on_device(tap_table, device, int(n_in), int(n_out))
 
 
 # ---- degradations as K-tap tables ------------------------------------------------------------------------------------------
@@ -99,7 +110,43 @@ _CV2_SMALL_GAUSSIAN = {3: (0.25, 0.5, 0.25), 5: (0.0625, 0.25, 0.375, 0.25, 0.06
 _OPTS = {"cubic": {}, "cubic+gaussian": {"blur_kernel": 3, "blur_sigma": 0.0}, "cubic_aa": {}, "fourier": {}}
 
 
-class Degradation:
+class _Frozen:
+    """A frozen, hashable value: ``kind``, ``opts`` (a sorted tuple of pairs) and whatever else the subclass names in
+    ``__slots__``, set once by ``_freeze``.  A kind's name is accepted wherever the value is (``of``)."""
+    __slots__ = ()
+
+    def _freeze(self, *fields):
+        for name, value in zip(self.__slots__, fields):
+            object.__setattr__(self, name, value)
+
+    def _key(self) -> tuple:
+        return tuple(getattr(self, name) for name in self.__slots__)
+
+    def __setattr__(self, name, value):
+        raise AttributeError(f"{type(self).__name__} is frozen")
+
+    __delattr__ = __setattr__
+
+    def __eq__(self, other):
+        return isinstance(other, type(self)) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        more = [f"{name}={getattr(self, name)!r}" for name in self.__slots__[2:]]
+        return type(self).__name__ + "(" + ", ".join([repr(self.kind)] + [f"{k}={v!r}" for k, v in self.opts] + more) + ")"
+
+    @classmethod
+    def of(cls, v):
+        if isinstance(v, cls):
+            return v
+        if isinstance(v, str):
+            return cls(v)
+        raise TypeError(f"a {cls.__name__.lower()} is a {cls.__name__} or the name of a kind, not {type(v).__name__}")
+
+
+class Degradation(_Frozen):
     """How an HR patch becomes its LR input: ``Degradation(kind='cubic', **opts)``, a frozen, hashable value.  A plain string
     is accepted wherever a ``Degradation`` is.  Kinds and options: ``'cubic'``; ``'cubic+gaussian'`` (``blur_kernel=3``: odd,
     3..7; ``blur_sigma=0``: cv2's fixed kernel if <= 0); ``'cubic_aa'``; ``'fourier'``.  ``operator_table`` defines them."""
@@ -121,30 +168,7 @@ class Degradation:
             if not math.isfinite(sg):
                 raise ValueError(f"Degradation: blur_sigma={full['blur_sigma']!r} must be finite")
             full = {"blur_kernel": int(bk), "blur_sigma": sg}
-        object.__setattr__(self, "kind", kind)
-        object.__setattr__(self, "opts", tuple(sorted(full.items())))
-
-    def __setattr__(self, name, value):
-        raise AttributeError("Degradation is frozen")
-
-    __delattr__ = __setattr__
-
-    def __eq__(self, other):
-        return isinstance(other, Degradation) and (self.kind, self.opts) == (other.kind, other.opts)
-
-    def __hash__(self):
-        return hash((self.kind, self.opts))
-
-    def __repr__(self):
-        return "Degradation(" + ", ".join([repr(self.kind)] + [f"{k}={v!r}" for k, v in self.opts]) + ")"
-
-    @classmethod
-    def of(cls, d: Union["Degradation", str]) -> "Degradation":
-        if isinstance(d, Degradation):
-            return d
-        if isinstance(d, str):
-            return cls(d)
-        raise TypeError(f"a degradation is a Degradation or the name of a kind, not {type(d).__name__}")
+        self._freeze(kind, tuple(sorted(full.items())))
 
     @classmethod
     def from_paras(cls, paras) -> "Degradation":
@@ -215,19 +239,29 @@ def _fourier_matrix(n_in: int, n_out: int) -> np.ndarray:
     return np.fft.irfft(Y, n_out, axis=0) * (n_out / n_in)
 
 
-def _table_of(M: np.ndarray, support: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
-    """A matrix (n_out, n_in) and the boolean mask of its taps -> ``(index, weight)`` of K columns."""
+def _table_of(M: np.ndarray, support: np.ndarray, empty_rows: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    """A matrix (n_out, n_in) and the boolean mask of its taps -> ``(index, weight)`` of K columns.  A row without taps is
+    refused, or with ``empty_rows`` left as weights 0.0 on index 0."""
     counts = support.sum(axis=1)
-    if counts.min() < 1:
+    if not empty_rows and counts.min() < 1:
         raise ValueError("operator_table: an output without taps")
     K = max(4, -(-int(counts.max()) // 4) * 4)
-    index = np.empty((M.shape[0], K), dtype=np.int32)
+    index = np.zeros((M.shape[0], K), dtype=np.int32)
     weight = np.zeros((M.shape[0], K), dtype=np.float64)
     for o in range(M.shape[0]):
         j = np.flatnonzero(support[o])
-        index[o, :len(j)], index[o, len(j):] = j, j[-1]
-        weight[o, :len(j)] = M[o, j]
+        if len(j):
+            index[o, :len(j)], index[o, len(j):] = j, j[-1]
+            weight[o, :len(j)] = M[o, j]
     return index, weight
+
+
+def _degradation_of(what: str, kind: Union[str, Degradation], opts: dict) -> Degradation:
+    """``kind`` with its options, or a ``Degradation`` (and then no options)."""
+    d = Degradation(kind, **opts) if isinstance(kind, str) else Degradation.of(kind)
+    if not isinstance(kind, str) and opts:
+        raise ValueError(f"{what}: options go with a kind's name, not with a Degradation")
+    return d
 
 
 def operator_table(kind: Union[str, Degradation], n_in: int, n_out: int, **opts) -> Tuple[np.ndarray, np.ndarray]:
@@ -260,9 +294,7 @@ def operator_table(kind: Union[str, Degradation], n_in: int, n_out: int, **opts)
     Dense: every sample is a tap, K = ``n_in`` rounded up to a multiple of 4; every row sums to 1.  Only ``n_out <= n_in``.
     A raw centred crop of k-space (``fftshift``, keep the middle ``n_out``, inverse transform) differs for even ``n_out``: it
     keeps the -Nyquist row alone, without its partner, so its result is complex and its real part carries half of that bin."""
-    d = Degradation(kind, **opts) if isinstance(kind, str) else Degradation.of(kind)
-    if not isinstance(kind, str) and opts:
-        raise ValueError("operator_table: options go with a kind's name, not with a Degradation")
+    d = _degradation_of("operator_table", kind, opts)
     n_in, n_out = int(n_in), int(n_out)
     if n_in <= 0 or n_out <= 0:
         raise ValueError(f"operator_table: sizes must be positive, got {n_in} -> {n_out}")
@@ -283,19 +315,9 @@ def operator_table(kind: Union[str, Degradation], n_in: int, n_out: int, **opts)
     return _table_of(M, np.ones(M.shape, dtype=bool))
 
 
-_OP_TABLES: Dict[tuple, Tuple[torch.Tensor, torch.Tensor]] = {}
-
-
 def _device_op_table(d: Degradation, n_in: int, n_out: int, device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
-    """``operator_table`` on the device, the weights rounded once to fp32; cached per (kind, options, in, out, device)."""
-    key = (d, int(n_in), int(n_out), device.type, device.index)
-    tab = _OP_TABLES.get(key)
-    if tab is None:
-        index, weight = operator_table(d, n_in, n_out)
-        tab = (torch.from_numpy(np.ascontiguousarray(index)).to(device),
-               torch.from_numpy(weight.astype(np.float32)).to(device))
-        _OP_TABLES[key] = tab
-    return tab
+    """``operator_table`` on the device; cached per (kind, options, in, out, device)."""
+    return _on_device(operator_table, device, d, int(n_in), int(n_out))
 
 
 def _need_gpu(what: str, *ts: torch.Tensor) -> None:
@@ -315,33 +337,53 @@ def _pair(size) -> Tuple[int, int]:
     return int(h), int(w)
 
 
+@contextlib.contextmanager
+def _whole_images(what: str, name: str, x, size=None):
+    """The front end of the whole-image calls: ``x`` must be a float32 CUDA tensor of 3 or 4 dimensions outside autograd, and
+    every size positive.  Yields ``(x as a contiguous (N, C, H, W), whether the result drops that N again, size as a pair)``
+    with ``x``'s device current."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{what}: {name} must be a torch tensor")
+    _need_gpu(what, x)
+    if x.requires_grad:
+        raise RuntimeError(f"{what} is not differentiable: detach the input")
+    if x.dtype != torch.float32:
+        raise TypeError(f"{what}: {name} must be float32, got {x.dtype}")
+    squeeze = x.dim() == 3
+    x4 = x.unsqueeze(0) if squeeze else x
+    if x4.dim() != 4:
+        raise ValueError(f"{what}: {name} must have 3 or 4 dimensions")
+    to = () if size is None else _pair(size)
+    if min(*x4.shape, *to) <= 0:
+        raise ValueError(f"{what}: sizes must be positive, got {tuple(x4.shape)}" + (f" -> {to}" if to else ""))
+    with torch.cuda.device(x.device):
+        yield x4.contiguous(), squeeze, to
+
+
 def bicubic_resize(x: torch.Tensor, size) -> torch.Tensor:
     """fp32 CUDA ``(N, C, H, W)`` (or ``(C, H, W)``) -> a new tensor of spatial ``size`` (an int or ``(oh, ow)``), down or up.
     Not differentiable."""
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("bicubic_resize: x must be a torch tensor")
-    _need_gpu("bicubic_resize", x)
-    if x.requires_grad:
-        raise RuntimeError("bicubic_resize is not differentiable: detach the input")
-    if x.dtype != torch.float32:
-        raise TypeError(f"bicubic_resize: x must be float32, got {x.dtype}")
-    squeeze = x.dim() == 3
-    if squeeze:
-        x = x.unsqueeze(0)
-    if x.dim() != 4:
-        raise ValueError("bicubic_resize: x must have 3 or 4 dimensions")
-    oh, ow = _pair(size)
-    N, C, H, W = x.shape
-    if min(N, C, H, W) <= 0 or oh <= 0 or ow <= 0:
-        raise ValueError(f"bicubic_resize: sizes must be positive, got {tuple(x.shape)} -> {(oh, ow)}")
-    x = x.contiguous()
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
+    with _whole_images("bicubic_resize", "x", x, size) as (x, squeeze, (oh, ow)):
+        N, C, H, W = x.shape
         iy, wy = _device_table(H, oh, x.device)
         ix, wx = _device_table(W, ow, x.device)
         y = torch.empty(N, C, oh, ow, dtype=torch.float32, device=x.device)
-        _lib.check(lib.rdst_resize_bicubic(x.data_ptr(), y.data_ptr(), N, C, H, W, oh, ow, iy.data_ptr(), wy.data_ptr(),
-                                           ix.data_ptr(), wx.data_ptr(), _stream()), "rdst_resize_bicubic")
+        _lib.check(_lib.load().rdst_resize_bicubic(x.data_ptr(), y.data_ptr(), N, C, H, W, oh, ow, iy.data_ptr(), wy.data_ptr(),
+                                                   ix.data_ptr(), wx.data_ptr(), _stream()), "rdst_resize_bicubic")
+    return y[0] if squeeze else y
+
+
+def _resample_sep(what: str, name: str, x, size, table) -> torch.Tensor:
+    """rdst_resample_sep of ``x`` to ``size`` under the tables ``table(n_in, n_out, device)`` of its two axes."""
+    with _whole_images(what, name, x, size) as (x, squeeze, (oh, ow)):
+        N, C, H, W = x.shape
+        iy, wy = table(H, oh, x.device)
+        ix, wx = table(W, ow, x.device)
+        y = torch.empty(N, C, oh, ow, dtype=torch.float32, device=x.device)
+        tmp = torch.empty(N * C * H * ow, dtype=torch.float32, device=x.device)
+        _lib.check(_lib.load().rdst_resample_sep(x.data_ptr(), y.data_ptr(), tmp.data_ptr(), N, C, H, W, oh, ow, iy.shape[1],
+                                                 iy.data_ptr(), wy.data_ptr(), ix.shape[1], ix.data_ptr(), wx.data_ptr(),
+                                                 _stream()), "rdst_resample_sep")
     return y[0] if squeeze else y
 
 
@@ -351,33 +393,7 @@ def resample(x: torch.Tensor, size, degradation: Union[str, Degradation] = "cubi
     (rdst_resample_sep: the horizontal sums, then the vertical chains).  With ``'cubic'`` it gives ``bicubic_resize``'s bits.
     Not differentiable."""
     d = Degradation.of(degradation)
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("resample: x must be a torch tensor")
-    _need_gpu("resample", x)
-    if x.requires_grad:
-        raise RuntimeError("resample is not differentiable: detach the input")
-    if x.dtype != torch.float32:
-        raise TypeError(f"resample: x must be float32, got {x.dtype}")
-    squeeze = x.dim() == 3
-    if squeeze:
-        x = x.unsqueeze(0)
-    if x.dim() != 4:
-        raise ValueError("resample: x must have 3 or 4 dimensions")
-    oh, ow = _pair(size)
-    N, C, H, W = x.shape
-    if min(N, C, H, W) <= 0 or oh <= 0 or ow <= 0:
-        raise ValueError(f"resample: sizes must be positive, got {tuple(x.shape)} -> {(oh, ow)}")
-    x = x.contiguous()
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        iy, wy = _device_op_table(d, H, oh, x.device)
-        ix, wx = _device_op_table(d, W, ow, x.device)
-        y = torch.empty(N, C, oh, ow, dtype=torch.float32, device=x.device)
-        tmp = torch.empty(N * C * H * ow, dtype=torch.float32, device=x.device)
-        _lib.check(lib.rdst_resample_sep(x.data_ptr(), y.data_ptr(), tmp.data_ptr(), N, C, H, W, oh, ow, iy.shape[1],
-                                         iy.data_ptr(), wy.data_ptr(), ix.shape[1], ix.data_ptr(), wx.data_ptr(), _stream()),
-                   "rdst_resample_sep")
-    return y[0] if squeeze else y
+    return _resample_sep("resample", "x", x, size, lambda n_in, n_out, dev: _device_op_table(d, n_in, n_out, dev))
 
 
 # ---- the adjoints of the K-tap operators --------------------------------------------------------------------------------
@@ -402,21 +418,8 @@ def adjoint_table(kind: Union[str, Degradation], n_in: int, n_out: int, **opts) 
     sample are merged by one float64 addition; taps of weight exactly 0.0 are left out); ``Kt`` is the longest row rounded up to a multiple of 4 and a shorter row is
     padded with weight 0.0 and its last index.  A source sample no output reads (``'cubic'`` 64 -> 8 and 24 -> 8 have such samples) gives a
     row of weights 0.0 and index 0."""
-    d = Degradation(kind, **opts) if isinstance(kind, str) else Degradation.of(kind)
-    if not isinstance(kind, str) and opts:
-        raise ValueError("adjoint_table: options go with a kind's name, not with a Degradation")
-    M, support = _operator_matrix(d, n_in, n_out)
-    MT, ST = M.T, support.T
-    counts = ST.sum(axis=1)
-    K = max(4, -(-int(counts.max()) // 4) * 4)
-    index = np.zeros((MT.shape[0], K), dtype=np.int32)
-    weight = np.zeros((MT.shape[0], K), dtype=np.float64)
-    for i in range(MT.shape[0]):
-        j = np.flatnonzero(ST[i])
-        if len(j):
-            index[i, :len(j)], index[i, len(j):] = j, j[-1]
-            weight[i, :len(j)] = MT[i, j]
-    return index, weight
+    M, support = _operator_matrix(_degradation_of("adjoint_table", kind, opts), n_in, n_out)
+    return _table_of(M.T, support.T, empty_rows=True)
 
 
 _OP_NORMS: Dict[tuple, float] = {}
@@ -424,28 +427,16 @@ _OP_NORMS: Dict[tuple, float] = {}
 
 def operator_norm(kind: Union[str, Degradation], n_in: int, n_out: int, **opts) -> float:
     """The spectral norm (largest singular value) of the float64 matrix of ``operator_table(kind, n_in, n_out)``."""
-    d = Degradation(kind, **opts) if isinstance(kind, str) else Degradation.of(kind)
-    if not isinstance(kind, str) and opts:
-        raise ValueError("operator_norm: options go with a kind's name, not with a Degradation")
+    d = _degradation_of("operator_norm", kind, opts)
     key = (d, int(n_in), int(n_out))
     if key not in _OP_NORMS:
         _OP_NORMS[key] = float(np.linalg.norm(_operator_matrix(d, n_in, n_out)[0], 2))
     return _OP_NORMS[key]
 
 
-_ADJ_TABLES: Dict[tuple, Tuple[torch.Tensor, torch.Tensor]] = {}
-
-
 def _device_adjoint_table(d: Degradation, n_in: int, n_out: int, device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
-    """``adjoint_table`` on the device, the weights rounded once to fp32; cached per (kind, options, in, out, device)."""
-    key = (d, int(n_in), int(n_out), device.type, device.index)
-    tab = _ADJ_TABLES.get(key)
-    if tab is None:
-        index, weight = adjoint_table(d, n_in, n_out)
-        tab = (torch.from_numpy(np.ascontiguousarray(index)).to(device),
-               torch.from_numpy(weight.astype(np.float32)).to(device))
-        _ADJ_TABLES[key] = tab
-    return tab
+    """``adjoint_table`` on the device; cached per (kind, options, in, out, device)."""
+    return _on_device(adjoint_table, device, d, int(n_in), int(n_out))
 
 
 def resample_adjoint(g: torch.Tensor, size, degradation: Union[str, Degradation] = "cubic") -> torch.Tensor:
@@ -453,34 +444,8 @@ def resample_adjoint(g: torch.Tensor, size, degradation: Union[str, Degradation]
     ``size = (H, W)``, ``A_y^T . g . A_x`` for the operators ``A`` of ``resample(x, (oh, ow), degradation)`` on an ``H x W``
     image.  It is rdst_resample_sep under the transposed tables (``adjoint_table``): the horizontal sums over the LR columns
     first, then the vertical chains, two launches.  Not differentiable."""
-    d = Degradation.of(degradation)
-    if not isinstance(g, torch.Tensor):
-        raise TypeError("resample_adjoint: g must be a torch tensor")
-    _need_gpu("resample_adjoint", g)
-    if g.requires_grad:
-        raise RuntimeError("resample_adjoint is not differentiable: detach the input")
-    if g.dtype != torch.float32:
-        raise TypeError(f"resample_adjoint: g must be float32, got {g.dtype}")
-    squeeze = g.dim() == 3
-    if squeeze:
-        g = g.unsqueeze(0)
-    if g.dim() != 4:
-        raise ValueError("resample_adjoint: g must have 3 or 4 dimensions")
-    H, W = _pair(size)
-    N, C, oh, ow = g.shape
-    if min(N, C, oh, ow) <= 0 or H <= 0 or W <= 0:
-        raise ValueError(f"resample_adjoint: sizes must be positive, got {tuple(g.shape)} -> {(H, W)}")
-    g = g.contiguous()
-    lib = _lib.load()
-    with torch.cuda.device(g.device):
-        iy, wy = _device_adjoint_table(d, H, oh, g.device)
-        ix, wx = _device_adjoint_table(d, W, ow, g.device)
-        y = torch.empty(N, C, H, W, dtype=torch.float32, device=g.device)
-        tmp = torch.empty(N * C * oh * W, dtype=torch.float32, device=g.device)
-        _lib.check(lib.rdst_resample_sep(g.data_ptr(), y.data_ptr(), tmp.data_ptr(), N, C, oh, ow, H, W, iy.shape[1],
-                                         iy.data_ptr(), wy.data_ptr(), ix.shape[1], ix.data_ptr(), wx.data_ptr(), _stream()),
-                   "rdst_resample_sep")
-    return y[0] if squeeze else y
+    d = Degradation.of(degradation)      # the table of an axis maps its LR samples to its HR ones: A's sizes, the other way round
+    return _resample_sep("resample_adjoint", "g", g, size, lambda n_lr, n_hr, dev: _device_adjoint_table(d, n_hr, n_lr, dev))
 
 
 class _Degrade(torch.autograd.Function):
@@ -534,7 +499,7 @@ def _noise_level(name: str, v) -> Union[float, Tuple[float, float]]:
     return f
 
 
-class Noise:
+class Noise(_Frozen):
     """The noise term of ``LR = A(HR) + n``: ``Noise(kind, **opts)``, a frozen, hashable value like ``Degradation``; a kind's
     name is accepted wherever a ``Noise`` is and stands for its default levels.  include/rdst_hip_noise.h defines the models.
 
@@ -560,31 +525,7 @@ class Noise:
             clip = (float(clip[0]), float(clip[1]))
             if math.isnan(clip[0]) or math.isnan(clip[1]) or clip[0] > clip[1]:
                 raise ValueError(f"Noise: clip={clip!r} must be a (lo, hi) pair with lo <= hi")
-        object.__setattr__(self, "kind", kind)
-        object.__setattr__(self, "opts", tuple(sorted(full.items())))
-        object.__setattr__(self, "clip", clip)
-
-    def __setattr__(self, name, value):
-        raise AttributeError("Noise is frozen")
-
-    __delattr__ = __setattr__
-
-    def __eq__(self, other):
-        return isinstance(other, Noise) and (self.kind, self.opts, self.clip) == (other.kind, other.opts, other.clip)
-
-    def __hash__(self):
-        return hash((self.kind, self.opts, self.clip))
-
-    def __repr__(self):
-        return "Noise(" + ", ".join([repr(self.kind)] + [f"{k}={v!r}" for k, v in self.opts] + [f"clip={self.clip!r}"]) + ")"
-
-    @classmethod
-    def of(cls, n: Union["Noise", str]) -> "Noise":
-        if isinstance(n, Noise):
-            return n
-        if isinstance(n, str):
-            return cls(n)
-        raise TypeError(f"a noise is a Noise or the name of a kind, not {type(n).__name__}")
+        self._freeze(kind, tuple(sorted(full.items())), clip)
 
     @classmethod
     def from_paras(cls, paras) -> Optional["Noise"]:
@@ -677,40 +618,25 @@ def add_noise(x: torch.Tensor, noise: Union[str, Noise], levels: Optional[torch.
     device nor reads from it.  ``return_draw=True`` returns ``(y, seed, levels)``, the levels as a host tensor (or the device
     tensor that was passed).  Not differentiable."""
     nz = Noise.of(noise)
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("add_noise: x must be a torch tensor")
-    _need_gpu("add_noise", x)
-    if x.requires_grad:
-        raise RuntimeError("add_noise is not differentiable: detach the input")
-    if x.dtype != torch.float32:
-        raise TypeError(f"add_noise: x must be float32, got {x.dtype}")
-    squeeze = x.dim() == 3
-    x4 = x.unsqueeze(0) if squeeze else x
-    if x4.dim() != 4:
-        raise ValueError("add_noise: x must have 3 or 4 dimensions")
-    N, C, H, W = x4.shape
-    if min(N, C, H, W) <= 0:
-        raise ValueError(f"add_noise: sizes must be positive, got {tuple(x4.shape)}")
-    if out is not None and (not isinstance(out, torch.Tensor) or out.shape != x.shape or out.dtype != torch.float32
-                            or out.device != x.device or not out.is_contiguous()):
-        raise ValueError(f"add_noise: out must be a contiguous float32 {tuple(x.shape)} tensor on {x.device}")
-    if out is not None and out.data_ptr() == x.data_ptr() and not x.is_contiguous():
-        raise ValueError("add_noise: in place needs a contiguous x")
-    if seed is None:
-        seed = _draw_seed(generator)
-    seed = int(seed) & _SEED_MASK
-    dev_levels = isinstance(levels, torch.Tensor) and levels.is_cuda
-    if levels is None:
-        levels = nz.levels_from(torch.rand(N, 2, generator=generator))
-    elif dev_levels:
-        if tuple(levels.shape) != (N, 2) or levels.dtype != torch.float32 or levels.device != x.device:
-            raise ValueError(f"add_noise: device levels must be a float32 ({N}, 2) tensor on {x.device}")
-        levels = levels.contiguous()
-    else:
-        levels = _host_levels(levels, N, "add_noise")
-    x4 = x4.contiguous()
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
+    with _whole_images("add_noise", "x", x) as (x4, squeeze, _):
+        N, C, H, W = x4.shape
+        if out is not None and (not isinstance(out, torch.Tensor) or out.shape != x.shape or out.dtype != torch.float32
+                                or out.device != x.device or not out.is_contiguous()):
+            raise ValueError(f"add_noise: out must be a contiguous float32 {tuple(x.shape)} tensor on {x.device}")
+        if out is not None and out.data_ptr() == x.data_ptr() and not x.is_contiguous():
+            raise ValueError("add_noise: in place needs a contiguous x")
+        if seed is None:
+            seed = _draw_seed(generator)
+        seed = int(seed) & _SEED_MASK
+        dev_levels = isinstance(levels, torch.Tensor) and levels.is_cuda
+        if levels is None:
+            levels = nz.levels_from(torch.rand(N, 2, generator=generator))
+        elif dev_levels:
+            if tuple(levels.shape) != (N, 2) or levels.dtype != torch.float32 or levels.device != x.device:
+                raise ValueError(f"add_noise: device levels must be a float32 ({N}, 2) tensor on {x.device}")
+            levels = levels.contiguous()
+        else:
+            levels = _host_levels(levels, N, "add_noise")
         # the seed on its 8-byte boundary, then the host levels: one pinned buffer, one copy
         buf = torch.empty(2 + (0 if dev_levels else 2 * N), dtype=torch.int32, pin_memory=True)
         buf[:2].view(torch.int64)[0] = _signed64(seed)
@@ -720,8 +646,8 @@ def add_noise(x: torch.Tensor, noise: Union[str, Noise], levels: Optional[torch.
         lv = levels.data_ptr() if dev_levels else dbuf.data_ptr() + 8
         y = out if out is not None else torch.empty(x.shape, dtype=torch.float32, device=x.device)
         lo, hi = nz.clip_range
-        _lib.check(lib.rdst_add_noise(x4.data_ptr(), y.data_ptr(), N, C, H, W, nz.model, lv, dbuf.data_ptr(), lo, hi, _stream()),
-                   "rdst_add_noise")
+        _lib.check(_lib.load().rdst_add_noise(x4.data_ptr(), y.data_ptr(), N, C, H, W, nz.model, lv, dbuf.data_ptr(), lo, hi,
+                                              _stream()), "rdst_add_noise")
     return (y, seed, levels) if return_draw else y
 
 
@@ -899,13 +825,10 @@ class DevicePatchSampler:
         k = int(torch.randint(len(self.sr_scales), (1,), generator=g)) if len(self.sr_scales) > 1 else 0
         hp = self.hr_patch_sizes[k]
         noisy = self.noise is not None
-        if not self.n_variants and not noisy:
-            tab = torch.empty(B, 3, dtype=torch.int32, pin_memory=self._pin)
-            var = None
-        else:       # one buffer, what else the kernel reads behind the index table: sample() copies it to the device as it is
-            vo, so, lo, total = self._layout(B, bool(self.n_variants), noisy)
-            both = torch.empty(total, dtype=torch.int32, pin_memory=self._pin)
-            tab, var = both[:3 * B].view(B, 3), both[vo:vo + B] if vo is not None else None
+        # one buffer: the index table and what else the kernel reads behind it; sample() copies it to the device as it is
+        vo, so, lo, total = self._layout(B, bool(self.n_variants), noisy)
+        both = torch.empty(total, dtype=torch.int32, pin_memory=self._pin)
+        tab, var = both[:3 * B].view(B, 3), both[vo:vo + B] if vo is not None else None
         tab[:, 0] = torch.randperm(self.S, generator=g)[:B]
         tab[:, 1] = torch.randint(0, self.H - hp + 1, (B,), generator=g)
         tab[:, 2] = torch.randint(0, self.W - hp + 1, (B,), generator=g)
@@ -935,8 +858,8 @@ class DevicePatchSampler:
         return vo, so, so + 2, so + 2 + 2 * B
 
     def _packed(self, d: Draw):
-        """The host buffer of a draw with variants, noise or both, and its ``_layout``.  A draw of ``draw()`` is one already;
-        forced tables are packed into a new one."""
+        """The host buffer of a draw and its ``_layout``.  A draw of ``draw()`` is one already; forced tables are packed into a
+        new one."""
         B, idx, var, lev = self.batch_size, d.indices, d.variants, d.noise_levels
         noisy = d.noise_seed is not None
         vo, so, lo, total = lay = self._layout(B, var is not None, noisy)
@@ -991,12 +914,10 @@ class DevicePatchSampler:
                             or not t.is_contiguous()):
                         raise ValueError(f"DevicePatchSampler.sample: out {name} must be a contiguous float32 {shape} tensor "
                                          f"on {self.device}")
-            if d.variants is None and not noisy:
-                index, variant = d.indices.to(self.device, non_blocking=True), None
-            else:       # the variants, the seed and the levels sit behind the 3 B int32 of the table, at _layout's offsets
-                both, (vo, so, lo, _) = self._packed(d)
-                index = both.to(self.device, non_blocking=True)
-                variant = index.data_ptr() + 4 * vo if vo is not None else None
+            # the variants, the seed and the levels sit behind the 3 B int32 of the table, at _layout's offsets
+            both, (vo, so, lo, _) = self._packed(d)
+            index = both.to(self.device, non_blocking=True)
+            variant = index.data_ptr() + 4 * vo if vo is not None else None
             lab = None
             if self.labels is not None:
                 lab = torch.empty(hr_shape[0], 1, hp, hp, dtype=torch.uint8, device=self.device)

@@ -135,6 +135,25 @@ def test_kernel_clamps_origins_it_was_not_promised(scale):
     assert torch.equal(b["in"], D.bicubic_resize(b["out"], lp))
 
 
+@pytest.mark.parametrize("lp", [120, 121], ids=["hp240-wide", "hp242-scalar"])
+def test_wide_patches_where_the_two_4tap_entries_band_differently(lp):
+    """rdst_sample_patches and rdst_sample_patches_d8 share one host plan and differ in its LDS budget: the transposing block
+    of the second takes 5376 bytes of the 64 KB.  At ratio 2 a band of 32 LR rows stages 67 HR rows, which fit the whole
+    budget up to hp = 244 (67 hp 4 <= 65536) and the reduced one up to hp = 224, so at hp = 240 and 242 the plain entry cuts
+    bands of 32 rows and the d8 entry bands of 16: other bands, the same batch."""
+    S, B, hp = 3, 2, 2 * lp
+    imgs, labels = _stack(S, 1, 250, 260, seed=lp)
+    s = D.DevicePatchSampler(imgs, B, lp, sr_scales=(2.0,), labels=labels, device=DEV, generator=torch.Generator().manual_seed(1))
+    d = s.draw()
+    b = s.sample(draw=d)
+    for k, (sl, top, left) in enumerate(d.indices.tolist()):
+        assert torch.equal(b["out"][k].cpu(), imgs[sl, :, top:top + hp, left:left + hp])
+        assert torch.equal(b["label"][k, 0].cpu(), labels[sl, top:top + hp, left:left + hp].long())
+    assert torch.equal(b["in"], D.bicubic_resize(b["out"], lp))
+    t = s.sample(draw=d._replace(variants=torch.zeros(B, dtype=torch.int32)))
+    assert torch.equal(t["in"], b["in"]) and torch.equal(t["out"], b["out"]) and torch.equal(t["label"], b["label"])
+
+
 def test_sampler_without_labels_and_with_several_scales():
     imgs, _ = _stack(6, 1, 40, 48, seed=2)
     s = D.DevicePatchSampler([a.permute(1, 2, 0).numpy() for a in imgs], 4, 8, sr_scales=(2.0, 3.0, 4.0), device=DEV,

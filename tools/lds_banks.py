@@ -143,7 +143,7 @@ def d8_blocks():
 
 
 def sampler_d8():
-    """rdst_amd/csrc/sampler.hip: sample4_d8_kernel / sample_tab_d8_kernel.  Their 32 x 32 blocks are the ones of d8_blocks()
+    """rdst_amd/csrc/sampler.hip: sample4_d8_kernel / sample_tab_kernel<V4, true>.  Their 32 x 32 blocks are the ones of d8_blocks()
     (thread = (r = tid / 8, q = tid % 8) in the 16-byte flavours, (tid / 32, tid % 32) in the scalar one; a flip mirrors r or
     the column inside the block, which permutes the banks of a lane group); sample4_d8_kernel adds hs[32][10], the horizontal
     sums: written at [r][q], read by lane = (oy = l / 8, ox = l % 8) at [4 oy + j][ox]."""
